@@ -16,6 +16,11 @@ Extra objects in the JSON line:
                 (events recorded on the library stream by pdwt_ktime_*), vs 8000 GB/s.
   cpu_baseline  the CPU oracle (plain-C restatement, OpenMP) timed on this host's cores on a
                 bounded sample of the same workload (rank 0, N = 1 only).
+
+--dump-outputs DIR writes what the last timed step of --config handed its caller (the reconstructed
+image(s), plus the value norm1() returned in c5) as DIR/<name>.npy, <= 64 MB in all (a fixed sample
+of a larger array); the timed steps then start from the seeded inputs, so two runs with the same
+arguments -- or two builds of the library -- can be compared array for array.
 """
 import argparse
 import ctypes as C
@@ -253,8 +258,9 @@ def pick_dominant(cfg, kernels, per_kernel_bytes, levels_eff):
     return dom, per_kernel_bytes[dom]
 
 
-def run_config(name, args, L, torch, dist, rank, world, steps, warmup, settle_ms, cpu_seconds, do_roofline):
-    """Time `steps` steps of config `name` on this rank's GPU; returns the fields of the JSON line for it."""
+def run_config(name, args, L, torch, dist, rank, world, steps, warmup, settle_ms, cpu_seconds, do_roofline, dump_dir=None):
+    """Time `steps` steps of config `name` on this rank's GPU; returns the fields of the JSON line for it.  `dump_dir`: write what the
+    last timed step computed there (dump_outputs)."""
     import numpy as np
     cfg = CONFIGS[name]
 
@@ -265,8 +271,12 @@ def run_config(name, args, L, torch, dist, rank, world, steps, warmup, settle_ms
     # synthetic input generated on the GPU that owns it (uniform [0,255), seed = rank)
     tdt = torch.float32 if cfg["dtype"] == "float32" else torch.float64
     g = torch.Generator(device="cuda")
-    g.manual_seed(1234 + rank)
-    img = torch.rand(cfg["Nr"], cfg["Nc"], device="cuda", dtype=tdt, generator=g) * 255.0
+
+    def make_input(bi):  # image bi of this rank's batch (bi = 0: the single image of the other configs)
+        g.manual_seed(1234 + rank + 1000 * bi)
+        return torch.rand(cfg["Nr"], cfg["Nc"], device="cuda", dtype=tdt, generator=g) * 255.0
+
+    img = make_input(0)
     torch.cuda.synchronize()
     B = None
     if world > 1:
@@ -292,14 +302,12 @@ def run_config(name, args, L, torch, dist, rank, world, steps, warmup, settle_ms
         # level plan (gridDim.y = image) -- at this size the two cascade launches + the level-3 launch of the single image
         stack = torch.empty(nbatch, cfg["Nr"], cfg["Nc"], device="cuda", dtype=tdt)
         for bi in range(nbatch):
-            g.manual_seed(1234 + rank + 1000 * bi)
-            stack[bi] = torch.rand(cfg["Nr"], cfg["Nc"], device="cuda", dtype=tdt, generator=g) * 255.0
+            stack[bi] = make_input(bi)
         torch.cuda.synchronize()
         IB = pdwt_amd_mod().ImageBatch(stack, cfg["wname"], cfg["levels"])
         del stack
     for bi in range(1, nbatch if IB is None else 1):  # the other images of the batch: distinct data, private instances (image + bands + scratch each)
-        g.manual_seed(1234 + rank + 1000 * bi)
-        xi = torch.rand(cfg["Nr"], cfg["Nc"], device="cuda", dtype=tdt, generator=g) * 255.0
+        xi = make_input(bi)
         torch.cuda.synchronize()
         Ws.append(pdwt_amd_mod().Wavelets(None, cfg["wname"], cfg["levels"], do_swt=cfg["do_swt"], ndim=cfg["ndim"], dtype=cfg["dtype"],
                                           shape=(cfg["Nr"], cfg["Nc"]), device_ptr=xi.data_ptr()))
@@ -315,10 +323,12 @@ def run_config(name, args, L, torch, dist, rank, world, steps, warmup, settle_ms
                 Wi.forward()
                 Wi.inverse()
     elif cfg["extra"]:
+        last_norm1 = [None]
+
         def step():
             W.forward()
             W.soft_threshold(0.5)
-            W.norm1()
+            last_norm1[0] = W.norm1()
             W.inverse()
     else:
         def step():
@@ -338,6 +348,12 @@ def run_config(name, args, L, torch, dist, rank, world, steps, warmup, settle_ms
         sync()
     for _ in range(warmup):
         step()
+    if dump_dir is not None:
+        # every step transforms the reconstruction of the one before it, and the settle phase above runs for a time, not a step count:
+        # the instances get their seeded inputs back, so that the K timed steps start from the same data in every run
+        insts = [IB[b] for b in range(nbatch)] if IB is not None else Ws
+        for bi, Wi in enumerate(insts):
+            Wi.set_image(make_input(bi))
     sync()
     barrier()
     sync()
@@ -353,6 +369,15 @@ def run_config(name, args, L, torch, dist, rank, world, steps, warmup, settle_ms
     elapsed = time.perf_counter() - t0
     wall1 = time.time()
     power = _SAMPLER.window(wall0, wall1) if _SAMPLER is not None else None
+    if dump_dir is not None:
+        # what a caller of the step holds afterwards: the reconstructed image(s) -- inverse() leaves the bands meaningless (W_INVERSE) --
+        # and, in the configs with the extra operators, the value norm1() returned
+        insts = [IB[b] for b in range(nbatch)] if IB is not None else Ws
+        pre = "r%d_" % rank if world > 1 else ""
+        outs = [(pre + ("img%02d_" % bi if nbatch > 1 else "") + "image", Wi.get_image()) for bi, Wi in enumerate(insts)]
+        if cfg["extra"]:
+            outs.append((pre + "norm1", np.array([last_norm1[0]], dtype=np.float64)))
+        dump_outputs(dump_dir, outs, DUMP_BYTES // world)
     # the same K steps once more between two HIP events on the library stream: `gpu_ms_per_step` (what the GPU spent between the first
     # kernel's start and the last one's end, without the bracket)
     sync()
@@ -726,6 +751,27 @@ _SAMPLER = None
 
 _PDWT = None
 
+DUMP_BYTES = 64 * 10**6  # all the arrays of one --dump-outputs directory, headers included
+
+
+def dump_outputs(out_dir, arrays, budget):
+    """Write each (name, array) as out_dir/<name>.npy, float32 or float64, at most `budget` bytes in all.  The budget is shared out
+    smallest array first; an array larger than its share is replaced by a fixed sample of its elements (flattened, ascending index
+    order, positions drawn by a RandomState seeded with the array's name) -- the same positions in every run."""
+    import zlib
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = sorted(arrays, key=lambda na: na[1].size)
+    left = budget - 256 * len(arrays)  # (room for the .npy headers)
+    for i, (name, a) in enumerate(arrays):
+        a = np.ascontiguousarray(a, dtype=np.float64 if a.dtype == np.float64 else np.float32)
+        k = min(a.size, max(left // (len(arrays) - i), 0) // a.itemsize)
+        if k < a.size:
+            pos = np.sort(np.random.RandomState(zlib.crc32(name.encode())).choice(a.size, k, replace=False))
+            a = a.reshape(-1)[pos]
+        left -= a.nbytes
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
 
 def pdwt_amd_mod():
     global _PDWT
@@ -750,6 +796,8 @@ def main():
     ap.add_argument("--no-others", action="store_true", help="skip the short runs of the other configs (other_configs)")
     ap.add_argument("--batch-instances", action="store_true", help="c2_batch: cycle 16 private Wavelets instances (one image per launch) instead of the ImageBatch entry")
     ap.add_argument("--settle-ms", type=float, default=150.0, help="untimed load before the warm-up steps (clock settling)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step of --config computed (reconstructed image, norm1) to DIR/<name>.npy, <= 64 MB in all")
     args = ap.parse_args()
 
     rank = int(os.environ.get("RANK", "0"))
@@ -789,8 +837,9 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
 
     global _SAMPLER
-    # every rank samples the clock and socket power of ITS device (N > 1: eight GPUs drawing power at once is what a scaling run is about)
-    _SAMPLER = PowerSampler(local_rank)
+    # every rank samples the clock and socket power of ITS device (N > 1: eight GPUs drawing power at once is what a scaling run is about);
+    # with all ranks on device 0 (PDWT_BENCH_ONE_GPU) rank 0 alone samples it
+    _SAMPLER = PowerSampler(local_rank) if os.environ.get("PDWT_BENCH_ONE_GPU") != "1" or rank == 0 else None
     time.sleep(0.5)  # (the helper imports amdsmi)
     # the size of the collective group, from the communicator itself: an all-reduce of one 1 per rank over the backend the batch split uses
     rccl_ranks, coll_backend = None, None
@@ -800,7 +849,8 @@ def main():
         dist.all_reduce(one)
         rccl_ranks = int(round(float(one.item())))
     cfg = CONFIGS[args.config]
-    res = run_config(args.config, args, L, torch, dist, rank, world, args.steps, args.warmup, args.settle_ms, args.cpu_seconds, not args.no_roofline)
+    res = run_config(args.config, args, L, torch, dist, rank, world, args.steps, args.warmup, args.settle_ms, args.cpu_seconds, not args.no_roofline,
+                     dump_dir=args.dump_outputs)
 
     # The other BASELINE configs, short runs in the same process (N = 1 only; the headline fields above stay those of --config)
     others = None

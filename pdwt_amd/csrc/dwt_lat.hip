@@ -121,6 +121,11 @@ __device__ __forceinline__ void lat_tile(int strips, int chunks, int RO, int nro
 #ifndef PDWT_LAT_NT  // (cache-policy experiments: bit 0 forward loads, bit 1 inverse loads, bit 2 forward stores, bit 3 inverse stores non-temporal)
 #define PDWT_LAT_NT 0
 #endif
+// The loads above are inline asm: the compiler's wait insertion does not see them, and once the last consumer of a register has run it
+// hands the register to other code while the load may still be in flight.  At the end of a kernel the prefetches of the last steps (rows
+// nobody consumes) are still outstanding: drain() waits for them with the register tied, so that nothing else is given it before the data
+// has landed (the clock probe's epilogue store once took its address offset from one of those registers).
+__device__ __forceinline__ void drain(v2d& d) { asm volatile("s_waitcnt vmcnt(0)" : "+v"(d) : : "memory"); }
 template <bool NT>
 __device__ __forceinline__ void asm_load(v2d& d, const char* p)
 {
@@ -467,6 +472,7 @@ __global__ __launch_bounds__(kNT, kWGPerCU) void k_fwd2d_lat(LatTable<LatGeo<HLE
             }
         });
     }
+    static_for<PF>([&](auto SL) { static_for<5>([&](auto MM) { drain(st[decltype(SL)::value][decltype(MM)::value]); }); });
     clock_probe_stamp(probe, 1, probe_all);
 }
 
@@ -728,6 +734,12 @@ __global__ __launch_bounds__(kNT, kWGPerCU) void k_inv2d_lat(LatTable<LatGeo<HLE
             }
         });
     }
+    static_for<PF>([&](auto SL) {
+        static_for<3>([&](auto MM) {
+            drain(sa[decltype(SL)::value][decltype(MM)::value]);
+            drain(sb[decltype(SL)::value][decltype(MM)::value]);
+        });
+    });
     clock_probe_stamp(probe, 1, probe_all);
 }
 

@@ -181,3 +181,26 @@ def test_hot_kernels_keep_their_taps_in_scalar_registers():
         share = c["v_readlane_b32"] / tot
         assert share <= lim, (k, c["v_readlane_b32"], tot)
         assert m.get("vgpr_spill_count", 0) == 0 and not any(op.startswith("scratch_") for op in c), (k, "scratch spills")
+
+
+def test_lattice_kernels_give_no_register_of_an_inflight_load_away():
+    """Static guard (no GPU): the lattice level kernels load with inline asm and hand-counted waits, which the compiler's wait insertion
+    does not see.  At the end of a kernel the prefetches of the last steps are still in flight; their registers once went to the clock
+    probe's epilogue store, which then took its address offset from a late-landing row of the image (an illegal access now and then, in
+    the bench's c5 clock probe).  tools/vmem_pending.py walks each kernel's control flow and reports every instruction that touches a
+    register a pending load will still write: none in these kernels."""
+    import importlib.util
+    if not os.path.exists("/opt/rocm/lib/llvm/bin/llvm-objdump"):
+        pytest.skip("no llvm-objdump")
+    spec = importlib.util.spec_from_file_location("vmem_pending", os.path.join(ROOT, "tools", "vmem_pending.py"))
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    ks = mod.disassemble()
+    dm = mod.demangle(sorted(ks))
+    checked = 0
+    for name, ins in ks.items():
+        if dm[name] in ("k_fwd2d_lat<40>", "k_inv2d_lat<40>"):
+            assert sum(1 for _, op, _, _ in ins if op.startswith("global_load")) > 10, dm[name]
+            assert mod.pending_uses(ins) == [], (dm[name], mod.pending_uses(ins)[:4])
+            checked += 1
+    assert checked == 2
