@@ -323,6 +323,48 @@ PDWT_DECL_UTILS(double, f64)
 PDWT_DECL_NONSEP(float, f32)
 PDWT_DECL_NONSEP(double, f64)
 
+/* ---------------------------------------------------------------------------------------------
+ * 3-D separable DWT (volumes; the reference rejects ndims == 3, src/wt.cu).  A row-major Nz x Nr x Nc volume, decimated and
+ * periodised exactly like the 1-D level of the drivers above, applied along x (Nc), then y (Nr), then z (Nz) at every level.
+ * Band order (pdwt_band_size3d, get_coeff): [A_L, then for levels L .. 1 the 7 detail bands of the level in the key order of
+ * PyWavelets' dwtn: aad, ada, add, daa, dad, dda, ddd] -- first letter = z axis, 'a' = low-pass, 'd' = high-pass -- so band
+ * 1 + 7*(L - lev) + k is detail k of level lev (1 = finest).  A level-lev band is div2^lev(Nz) x div2^lev(Nr) x div2^lev(Nc).
+ * All bands live in ONE zero-filled device allocation at 256-byte aligned offsets; band 0 is A_L only (no scratch role: the
+ * inverse leaves every band intact).  Levels are the caller's to clamp: at most ilog2(min(Nz, Nr, Nc) / (hlen - 1)).
+ * Sizes: any Nz <= 65535 and Nr * Nc < 2^31 (a plane is indexed in 32 bits; the volume itself may exceed 2^31 elements);
+ * anything else is PDWT_EINVAL / a NULL buffer / a scratch size of 0.
+ * d_tmp: pdwt_tmp_elems3d(info) elements, about 1.13x the volume (the four x-y quadrants of level 1 + one level-1 approximation).
+ * Kernels: pdwt_amd/csrc/dwt3d.hip, two launches per level and direction (an x-y tile kernel and a z kernel).
+ * The thresholds and norm1 follow the 2-D semantics (pdwt_soft_thresh_* / pdwt_hard_thresh_* / pdwt_norm1_*) with 7 detail
+ * bands per level: normalize > 0 divides beta by sqrt(2) per level, the approximation takes beta / sqrt(2)^L (soft) or the
+ * un-normalised beta (hard), norm1 sums |c| over all bands, band 0 included, in double.
+ * ------------------------------------------------------------------------------------------- */
+typedef struct pdwt_info3d {
+    int Nz;      /* planes */
+    int Nr;      /* rows per plane */
+    int Nc;      /* columns per row */
+    int nlevels; /* decomposition levels */
+    int hlen;    /* filter length */
+} pdwt_info3d;
+
+int pdwt_num_bands3d(pdwt_info3d info);                                                    /* 7L+1, or PDWT_EINVAL */
+long long pdwt_band_size3d(pdwt_info3d info, int num, int* band_Nz, int* band_Nr, int* band_Nc); /* elements, or PDWT_EINVAL */
+size_t pdwt_tmp_elems3d(pdwt_info3d info);                                                 /* 0 for a bad geometry */
+float** pdwt_create_coeffs_buffer3d_f32(pdwt_info3d info);
+double** pdwt_create_coeffs_buffer3d_f64(pdwt_info3d info);
+int pdwt_free_coeffs_buffer3d_f32(float** coeffs, pdwt_info3d info);
+int pdwt_free_coeffs_buffer3d_f64(double** coeffs, pdwt_info3d info);
+int pdwt_forward3d_separable_f32(float* d_image, float** d_coeffs, float* d_tmp, pdwt_info3d info, const pdwt_filters_f32* f);
+int pdwt_forward3d_separable_f64(double* d_image, double** d_coeffs, double* d_tmp, pdwt_info3d info, const pdwt_filters_f64* f);
+int pdwt_inverse3d_separable_f32(float* d_image, float** d_coeffs, float* d_tmp, pdwt_info3d info, const pdwt_filters_f32* f);
+int pdwt_inverse3d_separable_f64(double* d_image, double** d_coeffs, double* d_tmp, pdwt_info3d info, const pdwt_filters_f64* f);
+int pdwt_soft_thresh3d_f32(float** d_coeffs, float beta, pdwt_info3d info, int do_thresh_appcoeffs, int normalize);
+int pdwt_soft_thresh3d_f64(double** d_coeffs, double beta, pdwt_info3d info, int do_thresh_appcoeffs, int normalize);
+int pdwt_hard_thresh3d_f32(float** d_coeffs, float beta, pdwt_info3d info, int do_thresh_appcoeffs, int normalize);
+int pdwt_hard_thresh3d_f64(double** d_coeffs, double beta, pdwt_info3d info, int do_thresh_appcoeffs, int normalize);
+int pdwt_norm1_3d_f32(float** d_coeffs, pdwt_info3d info, double* out);   /* sum |c| in double (synchronises) */
+int pdwt_norm1_3d_f64(double** d_coeffs, pdwt_info3d info, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -1,0 +1,63 @@
+/*
+ * wt3d.h -- `Wavelets3D`: the separable, decimated, periodised 3-D DWT of a volume (no reference counterpart: the
+ * reference's Wavelets refuses ndims == 3).  Same build as wt.h: plain host C++, DTYPE = float (libpdwt.so) or double
+ * (-DDOUBLEPRECISION, libpdwtd.so), every device action a C-ABI call into libpdwt_hip.so (include/pdwt_hip.h).
+ *
+ * Volume: row-major Nz x Nr x Nc.  One level = the 1-D level of Wavelets(..., ndim=1) along x, then y, then z.
+ * Levels are clamped to ilog2(min(Nz, Nr, Nc) / (hlen - 1)); a clamp to 0 levels is W_CREATION_ERROR.
+ * Sizes: Nz <= 65535 and Nr * Nc < 2^31 (the volume itself may be larger, e.g. 2048^3); otherwise W_CREATION_ERROR.
+ * Device memory of an instance: the volume, the bands (about 1.0x the volume) and the scratch d_tmp (about 1.13x): ~3.1x the volume.
+ * Bands (get_coeff / set_coeff / coeff_int_ptr): 0 = A_L, then for levels L .. 1 the 7 detail bands of the level in the key
+ * order of PyWavelets' dwtn -- aad, ada, add, daa, dad, dda, ddd (first letter = z axis) -- so band 1 + 7*(L - lev) + k is
+ * detail k of level lev (1 = finest).  A level-lev band has div2^lev(Nz) x div2^lev(Nr) x div2^lev(Nc) elements.
+ * State machine: the w_state rules of Wavelets (threshold / get_coeff after inverse() are refused, inverse() twice is
+ * refused).  Not available in 3-D: SWT, non-separable and custom banks, cycle spinning, group_soft_threshold, shrink, proj_linf.
+ */
+#ifndef WT3D_H
+#define WT3D_H
+
+#include "wt.h"
+
+struct w_info3d {
+    int Nz;      /* planes */
+    int Nr;      /* rows per plane */
+    int Nc;      /* columns per row */
+    int nlevels; /* decomposition levels, after clamping */
+    int hlen;    /* filter length */
+};
+
+class Wavelets3D {
+  public:
+    DTYPE* d_image;   /* device: volume / reconstruction */
+    DTYPE** d_coeffs; /* host array of 7L+1 device pointers (one allocation) */
+    DTYPE* d_tmp;     /* device scratch */
+    char wname[128];
+    w_info3d winfos;
+    w_state state;
+
+    Wavelets3D(DTYPE* vol, int Nz, int Nr, int Nc, const char* wname, int levels, int memisonhost = 1);
+    ~Wavelets3D();
+
+    void forward();
+    void inverse();
+    void soft_threshold(DTYPE beta, int do_thresh_appcoeffs = 0, int normalize = 0);
+    void hard_threshold(DTYPE beta, int do_thresh_appcoeffs = 0, int normalize = 0);
+    DTYPE norm1();
+    double norm1_double(); /* norm1() before its rounding to DTYPE */
+    int get_image(DTYPE* vol);
+    void set_image(DTYPE* vol, int mem_is_on_device = 0);
+    int num_bands() const;
+    /* elements of band num (and its shape), 0 for a bad index */
+    long long band_shape(int num, int* bNz, int* bNr, int* bNc) const;
+    int get_coeff(DTYPE* coeff, int num);
+    void set_coeff(DTYPE* coeff, int num, int mem_is_on_device = 0);
+    intptr_t image_int_ptr(void);
+    intptr_t coeff_int_ptr(int num);
+
+  private:
+    void* filters_; /* per-instance bank + device */
+    Wavelets3D(const Wavelets3D&);
+    Wavelets3D& operator=(const Wavelets3D&);
+};
+
+#endif

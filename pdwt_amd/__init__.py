@@ -6,7 +6,8 @@ pdwt_amd/lib/libpdwt_hip.so) and the reference's own C++ ``Wavelets`` class abov
 libraries for tests, bench.py and Python callers -- the shape of the reference's external pypwt
 binding (README.md:24).
 """
-from ._native import Info, hip, host, require_gpu  # noqa: F401
+from ._native import Info, Info3D, hip, host, require_gpu  # noqa: F401
 from .wavelets import DeviceArray, ImageBatch, Wavelets, W_CREATION_ERROR, W_FORWARD, W_INIT, W_INVERSE  # noqa: F401
+from .wavelets3d import Wavelets3D  # noqa: F401
 
-__all__ = ["Wavelets", "ImageBatch", "DeviceArray", "Info", "hip", "host", "require_gpu"]
+__all__ = ["Wavelets", "Wavelets3D", "ImageBatch", "DeviceArray", "Info", "hip", "host", "require_gpu"]

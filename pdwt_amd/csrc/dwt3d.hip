@@ -1,0 +1,505 @@
+// dwt3d.hip -- the separable, decimated, periodised 3-D DWT (include/pdwt_hip.h "3-D separable DWT").
+//
+// One level = the reference's 1-D level (SURVEY A-1 / A-2: the decimating analysis and the zero-stuffing synthesis of
+// oracle/pdwt_oracle_impl.h ana_lines / syn_lines) along x, then y, then z, in TWO launches per level and direction:
+//   forward   x-y: volume (z, y, x) -> 4 quadrants (z, hy, hx) in d_tmp    one plane tile per workgroup, rows and columns in LDS
+//             z:   4 quadrants      -> the 8 bands (hz, hy, hx)           lanes across a plane, 16 outputs per thread along z
+//   inverse   z first (bands -> quadrants), then x-y (quadrants -> volume).
+// Per output sample the tap order and the one-FMA-per-tap accumulation are the oracle's: the 3-D result is bit-identical to
+// composing the 1-D level along the axes (Haar excepted, within 1 ulp: the oracle's 1-D Haar level scales a +- b in double).
+// Traffic per level: one read of the input (plus the tile halos) and one write of the quadrants, then one read of the quadrants
+// and one write of the bands -- twice the compulsory bytes of a fully fused level.
+#include "common.hpp"
+#include "bandlist.hpp"
+
+namespace pdwt {
+
+// ---- forward x-y level: one plane tile per workgroup ----------------------------------------------------
+// A workgroup owns FTY x FTX output positions (half resolution) of one plane z.  It stages the input rows / columns the tile
+// needs (with the periodic halo, wrap_ext per sample index) in LDS, runs the row pass into an LDS buffer (lo | hi per row)
+// and the column pass out of it, and writes the four quadrants (x band, y band) of the tile: one read of the plane (plus halo)
+// and one write of its four quadrants.  Per output the taps run j = 0 .. HL-1, one FMA each -- the oracle's row, then column.
+constexpr int kXYThreads = 256;
+constexpr int FTX = 32, FTY = 16;  // forward tile (output positions)
+constexpr int ITX = 64, ITY = 32;  // inverse tile (output samples, even starts)
+
+template <typename T>
+struct XYJob {
+    const T* src;     // forward: the level's input volume (z, ny, nx); inverse: unused
+    T* dst;           // inverse: the level's output volume; forward: unused
+    T* q[4];          // quadrants (z, hy, hx): index 2 * x band + y band (0 = low-pass)
+    int nx, ny, hx, hy;
+};
+
+template <typename T, int HL>
+constexpr size_t fwd_xy_lds()
+{
+    return sizeof(T) * ((size_t)(2 * FTY + HL - 2) * (2 * FTX + HL - 2) + 2 * (size_t)(2 * FTY + HL - 2) * FTX);
+}
+template <typename T, int HL>
+constexpr size_t inv_xy_lds()
+{
+    return sizeof(T) * (4 * (size_t)(ITY / 2 + HL / 2) * (ITX / 2 + HL / 2) + 2 * (size_t)ITY * (ITX / 2 + HL / 2));
+}
+
+// 0 that the compiler cannot see through: a tap index offset by it is not loop-invariant, so the scalar loads of the taps are
+// issued inside each loop instead of all hoisted in front of the loops (2*HL doubles of a long bank do not fit the SGPRs)
+__device__ __forceinline__ int opaque_zero()
+{
+    int z = 0;
+    asm volatile("" : "+s"(z));
+    return z;
+}
+
+template <typename T, int HL>
+__global__ __launch_bounds__(kXYThreads) void k_fwd_xy(XYJob<T> job, Taps2<T> taps)
+{
+    extern __shared__ double smem_d[];  // (double: 8-byte alignment for either precision)
+    constexpr int RI = 2 * FTY + HL - 2, CI = 2 * FTX + HL - 2, c = HL / 2 - 1;
+    T* in = reinterpret_cast<T*>(smem_d);  // [RI][CI]
+    T* rb = in + RI * CI;                  // [2][RI][FTX]: row pass lo | hi
+    const int tid = threadIdx.x, z = blockIdx.z;
+    const int ox0 = blockIdx.x * FTX, oy0 = blockIdx.y * FTY;
+    const int nx = job.nx, ny = job.ny;
+    const T* __restrict__ plane = job.src + (size_t)z * ny * nx;
+    const int gx0 = 2 * ox0 - c, gy0 = 2 * oy0 - c;
+    for (int e = tid; e < RI * CI; e += kXYThreads) {
+        const int r = e / CI, cc = e - r * CI;  // (compile-time divisor)
+        in[e] = plane[(size_t)wrap_ext(gy0 + r, ny) * nx + wrap_ext(gx0 + cc, nx)];
+    }
+    __syncthreads();
+    for (int e = tid; e < RI * FTX; e += kXYThreads) {
+        const int r = e / FTX, ox = e % FTX;
+        const T* p = in + r * CI + 2 * ox;
+        const int z0 = opaque_zero();
+        T sl = T(0), sh = T(0);
+#pragma unroll
+        for (int j = 0; j < HL; j++) {
+            const T v = p[j];
+            sl = fma_t<T>(v, taps.a[HL - 1 - j + z0], sl);
+            sh = fma_t<T>(v, taps.b[HL - 1 - j + z0], sh);
+        }
+        rb[e] = sl;
+        rb[RI * FTX + e] = sh;
+    }
+    __syncthreads();
+    const size_t zoff = (size_t)z * job.hy * job.hx;
+    for (int e = tid; e < FTY * FTX; e += kXYThreads) {
+        const int oy = e / FTX, ox = e % FTX;
+        if (oy0 + oy >= job.hy || ox0 + ox >= job.hx) continue;
+        const size_t o = zoff + (size_t)(oy0 + oy) * job.hx + (ox0 + ox);
+#pragma unroll
+        for (int xb = 0; xb < 2; xb++) {
+            const T* p = rb + xb * RI * FTX + (2 * oy) * FTX + ox;
+            const int z0 = opaque_zero();
+            T sl = T(0), sh = T(0);
+#pragma unroll
+            for (int j = 0; j < HL; j++) {
+                const T v = p[j * FTX];
+                sl = fma_t<T>(v, taps.a[HL - 1 - j + z0], sl);
+                sh = fma_t<T>(v, taps.b[HL - 1 - j + z0], sh);
+            }
+            job.q[2 * xb][o] = sl;
+            job.q[2 * xb + 1][o] = sh;
+        }
+    }
+}
+
+// ---- inverse x-y level: ITY x ITX output samples of one plane per workgroup ------------------------------
+// Stages the window of the four quadrants the tile needs (wrap_per), runs the synthesis along y into an LDS buffer (x low |
+// x high), then along x into the output.  Synthesis rule of the oracle's syn_lines, the two branch sums added once.
+template <typename T, int HL>
+__global__ __launch_bounds__(kXYThreads) void k_inv_xy(XYJob<T> job, Taps2<T> taps)
+{
+    extern __shared__ double smem_d[];
+    constexpr int h2 = HL / 2, c = h2 / 2, shift = (h2 & 1) ? 0 : 1;
+    constexpr int WR = ITY / 2 + h2, WC = ITX / 2 + h2;
+    T* in = reinterpret_cast<T*>(smem_d);  // [4][WR][WC]
+    T* cb = in + 4 * WR * WC;              // [2][ITY][WC]: y synthesis of the x-low / x-high pairs
+    const int tid = threadIdx.x, z = blockIdx.z;
+    const int g0x = blockIdx.x * ITX, g0y = blockIdx.y * ITY;  // even
+    const int hx = job.hx, hy = job.hy;
+    const int wx0 = g0x / 2 - c, wy0 = g0y / 2 - c;
+    const size_t zoff = (size_t)z * hy * hx;
+    for (int e = tid; e < 4 * WR * WC; e += kXYThreads) {
+        const int qd = e / (WR * WC), rem = e - qd * (WR * WC), r = rem / WC, cc = rem - r * WC;
+        in[e] = job.q[qd][zoff + (size_t)wrap_per(wy0 + r, hy) * hx + wrap_per(wx0 + cc, hx)];
+    }
+    __syncthreads();
+    for (int e = tid; e < 2 * ITY * WC; e += kXYThreads) {
+        const int xb = e / (ITY * WC), rem = e - xb * (ITY * WC), gy = rem / WC, cc = rem - gy * WC;
+        const int gp = gy + shift, lp = gp >> 1;
+        const bool odd_tap = (gp & 1) == 0;
+        const T* pa = in + (2 * xb) * WR * WC + lp * WC + cc;
+        const T* pd = pa + WR * WC;
+        T sa = T(0), sd = T(0);
+#pragma unroll
+        for (int j = 0; j < h2; j++) {
+            const T fl = odd_tap ? taps.a[HL - 2 - 2 * j] : taps.a[HL - 1 - 2 * j];
+            const T fh = odd_tap ? taps.b[HL - 2 - 2 * j] : taps.b[HL - 1 - 2 * j];
+            sa = fma_t<T>(pa[j * WC], fl, sa);
+            sd = fma_t<T>(pd[j * WC], fh, sd);
+        }
+        cb[e] = sa + sd;
+    }
+    __syncthreads();
+    const int nx = job.nx, ny = job.ny;
+    T* __restrict__ plane = job.dst + (size_t)z * ny * nx;
+    for (int e = tid; e < ITY * ITX; e += kXYThreads) {
+        const int gy = e / ITX, gx = e % ITX;
+        if (g0y + gy >= ny || g0x + gx >= nx) continue;
+        const int gp = gx + shift, lp = gp >> 1;
+        const bool odd_tap = (gp & 1) == 0;
+        const T* pa = cb + gy * WC + lp;
+        const T* pd = pa + ITY * WC;
+        T sa = T(0), sd = T(0);
+#pragma unroll
+        for (int j = 0; j < h2; j++) {
+            const T fl = odd_tap ? taps.a[HL - 2 - 2 * j] : taps.a[HL - 1 - 2 * j];
+            const T fh = odd_tap ? taps.b[HL - 2 - 2 * j] : taps.b[HL - 1 - 2 * j];
+            sa = fma_t<T>(pa[j], fl, sa);
+            sd = fma_t<T>(pd[j], fh, sd);
+        }
+        plane[(size_t)(g0y + gy) * nx + (g0x + gx)] = sa + sd;
+    }
+}
+
+// ---- z pass: ZC outputs per thread along z from a register window -----------------------------------------
+// Lanes run across a plane (coalesced), blockIdx.y = chunk of ZC outputs along z, blockIdx.z = quadrant.  The thread loads the
+// 2*ZC + HL - 2 input planes of its chunk ONCE into registers and computes every output of the chunk from them.
+constexpr int kZThreads = 256;
+constexpr int ZC = 16;
+
+template <typename T>
+struct ZJob {
+    const T* src[4];  // forward: quadrants (nz planes); inverse: low branches (nin planes)
+    const T* src2[4]; // inverse: high branches
+    T* lo[4];         // forward: low outputs; inverse: outputs
+    T* hi[4];         // forward: high outputs
+    int nin, nout, plane;
+};
+
+template <typename T, int HL>
+__global__ __launch_bounds__(kZThreads) void k_ana_z(ZJob<T> job, Taps2<T> taps)
+{
+    const int k = blockIdx.x * kZThreads + threadIdx.x;
+    if (k >= job.plane) return;
+    const int e = blockIdx.z, i0 = blockIdx.y * ZC;
+    constexpr int c = HL / 2 - 1, W = 2 * ZC + HL - 2;
+    const int n = job.nin, s0 = 2 * i0 - c;
+    const size_t pl = (size_t)job.plane;
+    const T* __restrict__ x = job.src[e] + k;
+    T v[W];
+#pragma unroll
+    for (int w = 0; w < W; w++) v[w] = x[(size_t)wrap_ext(s0 + w, n) * pl];
+    T* __restrict__ lo = job.lo[e] + k;
+    T* __restrict__ hi = job.hi[e] + k;
+#pragma unroll
+    for (int u = 0; u < ZC; u++) {
+        if (i0 + u < job.nout) {
+            T sl = T(0), sh = T(0);
+#pragma unroll
+            for (int j = 0; j < HL; j++) {
+                sl = fma_t<T>(v[2 * u + j], taps.a[HL - 1 - j], sl);
+                sh = fma_t<T>(v[2 * u + j], taps.b[HL - 1 - j], sh);
+            }
+            lo[(size_t)(i0 + u) * pl] = sl;
+            hi[(size_t)(i0 + u) * pl] = sh;
+        }
+    }
+}
+
+template <typename T, int HL>
+__global__ __launch_bounds__(kZThreads) void k_syn_z(ZJob<T> job, Taps2<T> taps)
+{
+    const int k = blockIdx.x * kZThreads + threadIdx.x;
+    if (k >= job.plane) return;
+    const int e = blockIdx.z, g0 = blockIdx.y * ZC;  // even
+    constexpr int h2 = HL / 2, c = h2 / 2, shift = (h2 & 1) ? 0 : 1, W = ZC / 2 + h2;
+    const int nin = job.nin, q0 = g0 / 2 - c;
+    const size_t pl = (size_t)job.plane;
+    const T* __restrict__ a = job.src[e] + k;
+    const T* __restrict__ d = job.src2[e] + k;
+    T va[W], vd[W];
+#pragma unroll
+    for (int w = 0; w < W; w++) {
+        const size_t s = (size_t)wrap_per(q0 + w, nin) * pl;
+        va[w] = a[s];
+        vd[w] = d[s];
+    }
+    T* __restrict__ out = job.lo[e] + k;
+#pragma unroll
+    for (int u = 0; u < ZC; u++) {
+        if (g0 + u < job.nout) {
+            const int gp = u + shift, lp = gp >> 1, off = 1 - (gp & 1);  // compile-time after unrolling
+            T sa = T(0), sd = T(0);
+#pragma unroll
+            for (int j = 0; j < h2; j++) {
+                sa = fma_t<T>(va[lp + j], taps.a[HL - 1 - (2 * j + off)], sa);
+                sd = fma_t<T>(vd[lp + j], taps.b[HL - 1 - (2 * j + off)], sd);
+            }
+            out[(size_t)(g0 + u) * pl] = sa + sd;
+        }
+    }
+}
+
+#define PDWT_CHECK_LAUNCH3() PDWT_HIP_TRY(hipGetLastError())
+
+template <typename T, int HL>
+static int launch_level(int dir, int pass, const XYJob<T>& xy, const ZJob<T>& zj, int nz, const Taps2<T>& taps)
+{
+    if (pass == 0) {  // x-y
+        const bool fwd = dir == 0;
+        const size_t lds = fwd ? fwd_xy_lds<T, HL>() : inv_xy_lds<T, HL>();
+        const void* kfn = fwd ? (const void*)k_fwd_xy<T, HL> : (const void*)k_inv_xy<T, HL>;
+        if (lds > 64 * 1024)
+            if (const int rc = lds_opt_in_ptr(kfn); rc != PDWT_OK) return rc;
+        const dim3 grid = fwd ? dim3(idiv_up(xy.hx, FTX), idiv_up(xy.hy, FTY), nz) : dim3(idiv_up(xy.nx, ITX), idiv_up(xy.ny, ITY), nz);
+        if (fwd) hipLaunchKernelGGL((k_fwd_xy<T, HL>), grid, dim3(kXYThreads), lds, stream(), xy, taps);
+        else hipLaunchKernelGGL((k_inv_xy<T, HL>), grid, dim3(kXYThreads), lds, stream(), xy, taps);
+    } else {  // z
+        const dim3 grid(idiv_up(zj.plane, kZThreads), idiv_up(zj.nout, ZC), 4);
+        if (dir == 0) hipLaunchKernelGGL((k_ana_z<T, HL>), grid, dim3(kZThreads), 0, stream(), zj, taps);
+        else hipLaunchKernelGGL((k_syn_z<T, HL>), grid, dim3(kZThreads), 0, stream(), zj, taps);
+    }
+    PDWT_CHECK_LAUNCH3();
+    return PDWT_OK;
+}
+
+// every even length of the bank table (2 .. 40)
+template <typename T, int HL = 2>
+static int run_pass(int hlen, int dir, int pass, const XYJob<T>& xy, const ZJob<T>& zj, int nz, const Taps2<T>& taps)
+{
+    if constexpr (HL > PDWT_MAX_FILTER_WIDTH) {
+        return PDWT_EINVAL;
+    } else {
+        if (hlen == HL) return launch_level<T, HL>(dir, pass, xy, zj, nz, taps);
+        return run_pass<T, HL + 2>(hlen, dir, pass, xy, zj, nz, taps);
+    }
+}
+
+// ---- geometry ------------------------------------------------------------------------------------
+constexpr int k3MaxLevels = 13;  // 7*13 + 1 = 92 bands <= the 97 of the band-table kernels (utils.hip)
+
+struct Geom3 {
+    int L;
+    int z[k3MaxLevels + 1], y[k3MaxLevels + 1], x[k3MaxLevels + 1];  // level-l volume, l = 0 .. L
+};
+static bool geom3(const pdwt_info3d& w, Geom3* g)
+{
+    if (w.Nz < 1 || w.Nr < 1 || w.Nc < 1 || w.nlevels < 1 || w.nlevels > k3MaxLevels) return false;
+    // a plane is indexed with 32 bits (lanes across it) and z is a grid dimension: Nr * Nc < 2^31, Nz <= 65535
+    if ((unsigned long long)w.Nr * (unsigned long long)w.Nc >= (1ull << 31) || w.Nz > 65535) return false;
+    g->L = w.nlevels;
+    g->z[0] = w.Nz;
+    g->y[0] = w.Nr;
+    g->x[0] = w.Nc;
+    for (int l = 1; l <= w.nlevels; l++) {
+        g->z[l] = div2(g->z[l - 1]);
+        g->y[l] = div2(g->y[l - 1]);
+        g->x[l] = div2(g->x[l - 1]);
+    }
+    return true;
+}
+static size_t pad64(size_t n) { return (n + 63) & ~(size_t)63; }  // 256-byte multiples for either precision
+
+// d_tmp = [Q: the 4 quadrants (z, hy, hx) | A: hz*hy*hx] at level-1 geometry (the largest of every level)
+struct Tmp3 {
+    size_t q, abuf, total;
+};
+static Tmp3 tmp3(const Geom3& g)
+{
+    Tmp3 t;
+    const size_t z = g.z[0], hz = g.z[1], hy = g.y[1], hx = g.x[1];
+    t.q = 0;
+    t.abuf = pad64(4 * z * hy * hx);
+    t.total = t.abuf + pad64(hz * hy * hx);
+    return t;
+}
+
+// band index of detail k (0..6: aad, ada, add, daa, dad, dda, ddd) of level lev (1 = finest)
+static inline int band3(int L, int lev, int k) { return 1 + 7 * (L - lev) + k; }
+
+// the z pass pairs: quadrant q (2 * x band + y band) -> (z low, z high) detail index of the level (-1: the approximation)
+//   q0 (y a, x a): aaa, daa    q1 (y d, x a): ada, dda    q2 (y a, x d): aad, dad    q3 (y d, x d): add, ddd
+static const int kZLow[4] = {-1, 1, 0, 2}, kZHigh[4] = {3, 5, 4, 6};
+
+template <typename T>
+static int forward3d(T* img, T** c, T* tmp, pdwt_info3d w, const typename FiltersOf<T>::type* f)
+{
+    Geom3 g;
+    if (!img || !c || !tmp || !f || !geom3(w, &g) || f->hlen != w.hlen || w.hlen < 2 || (w.hlen & 1)) return PDWT_EINVAL;
+    const Taps2<T> taps = taps_fwd<T>(f);
+    const Tmp3 tl = tmp3(g);
+    T* const qb = tmp + tl.q;
+    T* const abuf = tmp + tl.abuf;
+    for (int l = 0; l < g.L; l++) {
+        const int lev = l + 1;
+        const size_t sq = (size_t)g.z[l] * g.y[l + 1] * g.x[l + 1];
+        XYJob<T> xy{};
+        xy.src = (l == 0) ? img : abuf;
+        for (int q = 0; q < 4; q++) xy.q[q] = qb + q * sq;
+        xy.nx = g.x[l], xy.ny = g.y[l], xy.hx = g.x[l + 1], xy.hy = g.y[l + 1];
+        ZJob<T> zj{};
+        for (int q = 0; q < 4; q++) {
+            zj.src[q] = qb + q * sq;
+            zj.lo[q] = (q == 0) ? ((lev == g.L) ? c[0] : abuf) : c[band3(g.L, lev, kZLow[q])];
+            zj.hi[q] = c[band3(g.L, lev, kZHigh[q])];
+        }
+        zj.nin = g.z[l], zj.nout = g.z[l + 1], zj.plane = g.y[l + 1] * g.x[l + 1];
+        // x-y into the quadrants (reads the level's input), then z into the bands (may overwrite abuf: already read)
+        if (const int rc = run_pass<T>(w.hlen, 0, 0, xy, zj, g.z[l], taps); rc != PDWT_OK) return rc;
+        if (const int rc = run_pass<T>(w.hlen, 0, 1, xy, zj, g.z[l], taps); rc != PDWT_OK) return rc;
+    }
+    return PDWT_OK;
+}
+
+template <typename T>
+static int inverse3d(T* img, T** c, T* tmp, pdwt_info3d w, const typename FiltersOf<T>::type* f)
+{
+    Geom3 g;
+    if (!img || !c || !tmp || !f || !geom3(w, &g) || f->hlen != w.hlen || w.hlen < 2 || (w.hlen & 1)) return PDWT_EINVAL;
+    const Taps2<T> taps = taps_inv<T>(f);
+    const Tmp3 tl = tmp3(g);
+    T* const qb = tmp + tl.q;
+    T* const abuf = tmp + tl.abuf;
+    for (int l = g.L - 1; l >= 0; l--) {
+        const int lev = l + 1;
+        const size_t sq = (size_t)g.z[l] * g.y[l + 1] * g.x[l + 1];
+        ZJob<T> zj{};
+        for (int q = 0; q < 4; q++) {
+            zj.src[q] = (q == 0) ? ((lev == g.L) ? c[0] : abuf) : c[band3(g.L, lev, kZLow[q])];
+            zj.src2[q] = c[band3(g.L, lev, kZHigh[q])];
+            zj.lo[q] = qb + q * sq;
+        }
+        zj.nin = g.z[l + 1], zj.nout = g.z[l], zj.plane = g.y[l + 1] * g.x[l + 1];
+        XYJob<T> xy{};
+        for (int q = 0; q < 4; q++) xy.q[q] = qb + q * sq;
+        xy.dst = (l == 0) ? img : abuf;
+        xy.nx = g.x[l], xy.ny = g.y[l], xy.hx = g.x[l + 1], xy.hy = g.y[l + 1];
+        // z into the quadrants (reads abuf), then x-y into the level's output (may overwrite abuf: already read)
+        if (const int rc = run_pass<T>(w.hlen, 1, 1, xy, zj, g.z[l], taps); rc != PDWT_OK) return rc;
+        if (const int rc = run_pass<T>(w.hlen, 1, 0, xy, zj, g.z[l], taps); rc != PDWT_OK) return rc;
+    }
+    return PDWT_OK;
+}
+
+// ---- band table ----------------------------------------------------------------------------------
+static long long band_size3(const pdwt_info3d& w, int num, int* bz, int* by, int* bx)
+{
+    Geom3 g;
+    if (!geom3(w, &g) || num < 0 || num > 7 * g.L) return PDWT_EINVAL;
+    const int lev = (num == 0) ? g.L : g.L - (num - 1) / 7;
+    if (bz) *bz = g.z[lev];
+    if (by) *by = g.y[lev];
+    if (bx) *bx = g.x[lev];
+    return (long long)g.z[lev] * g.y[lev] * g.x[lev];
+}
+
+template <typename T>
+static T** create3(pdwt_info3d w)
+{
+    Geom3 g;
+    if (!geom3(w, &g)) return nullptr;
+    const int nb = 7 * g.L + 1;
+    size_t off[7 * k3MaxLevels + 1];
+    size_t total = 0;
+    for (int k = 0; k < nb; k++) {
+        off[k] = total;
+        total += ((size_t)band_size3(w, k, nullptr, nullptr, nullptr) * sizeof(T) + 255) & ~(size_t)255;
+    }
+    char* base = (char*)pdwt_malloc(total);
+    if (!base) return nullptr;
+    if (pdwt_memset(base, 0, total) != PDWT_OK) {
+        (void)pdwt_free(base);
+        return nullptr;
+    }
+    T** tab = (T**)calloc((size_t)nb + 1, sizeof(T*));  // slot [-1]: the allocation base (as coeffs.hip)
+    if (!tab) {
+        (void)pdwt_free(base);
+        return nullptr;
+    }
+    tab[0] = (T*)base;
+    for (int k = 0; k < nb; k++) tab[k + 1] = (T*)(base + off[k]);
+    return tab + 1;
+}
+template <typename T>
+static int destroy3(T** c)
+{
+    if (!c) return PDWT_OK;
+    const int rc = pdwt_free((void*)c[-1]);
+    free(c - 1);
+    return rc;
+}
+
+// thresholds: the 2-D rules of utils.hip ew_bands with 7 detail bands per level
+template <typename T>
+static int thresh3(int op, T** c, T beta, pdwt_info3d w, int do_thresh_appcoeffs, int normalize)
+{
+    Geom3 g;
+    if (!c || !geom3(w, &g)) return PDWT_EINVAL;
+    T* ptr[7 * k3MaxLevels + 1];
+    size_t n[7 * k3MaxLevels + 1];
+    T b[7 * k3MaxLevels + 1];
+    int nb = 0;
+    if (do_thresh_appcoeffs) {
+        T beta2 = beta;
+        if (normalize > 0 && op == BL_SOFT) {  // beta / sqrt(2)^nlevels, as in 2-D (src/common.cu:231-235)
+            const int nl2 = g.L / 2;
+            beta2 /= (T)(1 << nl2);
+            if (nl2 * 2 != g.L) beta2 = (T)(beta2 / 1.4142135623730951);
+        }
+        ptr[nb] = c[0], n[nb] = (size_t)band_size3(w, 0, nullptr, nullptr, nullptr), b[nb] = beta2, nb++;
+    }
+    for (int lev = 1; lev <= g.L; lev++) {
+        if (normalize > 0) beta = (T)(beta / 1.4142135623730951);
+        for (int k = 0; k < 7; k++) {
+            const int num = band3(g.L, lev, k);
+            ptr[nb] = c[num], n[nb] = (size_t)band_size3(w, num, nullptr, nullptr, nullptr), b[nb] = beta, nb++;
+        }
+    }
+    return band_list_ew<T>(op, ptr, n, b, nb);
+}
+template <typename T>
+static int norm1_3(T** c, pdwt_info3d w, double* out)
+{
+    Geom3 g;
+    if (!c || !out || !geom3(w, &g)) return PDWT_EINVAL;
+    T* ptr[7 * k3MaxLevels + 1];
+    size_t n[7 * k3MaxLevels + 1];
+    const int nb = 7 * g.L + 1;
+    for (int k = 0; k < nb; k++) ptr[k] = c[k], n[k] = (size_t)band_size3(w, k, nullptr, nullptr, nullptr);
+    return band_list_abs_sum<T>(ptr, n, nb, out);
+}
+
+}  // namespace pdwt
+
+using namespace pdwt;
+
+extern "C" {
+int pdwt_num_bands3d(pdwt_info3d w)
+{
+    Geom3 g;
+    return geom3(w, &g) ? 7 * g.L + 1 : PDWT_EINVAL;
+}
+long long pdwt_band_size3d(pdwt_info3d w, int num, int* bz, int* by, int* bx) { return band_size3(w, num, bz, by, bx); }
+size_t pdwt_tmp_elems3d(pdwt_info3d w)
+{
+    Geom3 g;
+    return geom3(w, &g) ? tmp3(g).total : 0;
+}
+float** pdwt_create_coeffs_buffer3d_f32(pdwt_info3d w) { return create3<float>(w); }
+double** pdwt_create_coeffs_buffer3d_f64(pdwt_info3d w) { return create3<double>(w); }
+int pdwt_free_coeffs_buffer3d_f32(float** c, pdwt_info3d) { return destroy3(c); }
+int pdwt_free_coeffs_buffer3d_f64(double** c, pdwt_info3d) { return destroy3(c); }
+int pdwt_forward3d_separable_f32(float* img, float** c, float* tmp, pdwt_info3d w, const pdwt_filters_f32* f) { return forward3d<float>(img, c, tmp, w, f); }
+int pdwt_forward3d_separable_f64(double* img, double** c, double* tmp, pdwt_info3d w, const pdwt_filters_f64* f) { return forward3d<double>(img, c, tmp, w, f); }
+int pdwt_inverse3d_separable_f32(float* img, float** c, float* tmp, pdwt_info3d w, const pdwt_filters_f32* f) { return inverse3d<float>(img, c, tmp, w, f); }
+int pdwt_inverse3d_separable_f64(double* img, double** c, double* tmp, pdwt_info3d w, const pdwt_filters_f64* f) { return inverse3d<double>(img, c, tmp, w, f); }
+int pdwt_soft_thresh3d_f32(float** c, float beta, pdwt_info3d w, int app, int norm) { return thresh3<float>(BL_SOFT, c, beta, w, app, norm); }
+int pdwt_soft_thresh3d_f64(double** c, double beta, pdwt_info3d w, int app, int norm) { return thresh3<double>(BL_SOFT, c, beta, w, app, norm); }
+int pdwt_hard_thresh3d_f32(float** c, float beta, pdwt_info3d w, int app, int norm) { return thresh3<float>(BL_HARD, c, beta, w, app, norm); }
+int pdwt_hard_thresh3d_f64(double** c, double beta, pdwt_info3d w, int app, int norm) { return thresh3<double>(BL_HARD, c, beta, w, app, norm); }
+int pdwt_norm1_3d_f32(float** c, pdwt_info3d w, double* out) { return norm1_3<float>(c, w, out); }
+int pdwt_norm1_3d_f64(double** c, pdwt_info3d w, double* out) { return norm1_3<double>(c, w, out); }
+}

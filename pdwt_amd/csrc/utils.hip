@@ -19,6 +19,7 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "bandlist.hpp"
 
 namespace pdwt {
 
@@ -725,3 +726,63 @@ int pdwt_sum_scratch_read(const double* scratch, double* out)
 PDWT_UTILS_API(f32, float)
 PDWT_UTILS_API(f64, double)
 }
+
+namespace pdwt {
+// explicit band lists (bandlist.hpp): the same kernels as ew_bands / band_sum_double above, the table filled by the caller
+template <typename T>
+int band_list_ew(int op, T* const* ptr, const size_t* n, const T* beta, int nb)
+{
+    if (!ptr || !n || !beta || nb < 1 || nb > kMaxBands) return PDWT_EINVAL;
+    BandTable<T> tab;
+    tab.nb = 0;
+    tab.chunk0[0] = 0;
+    bool vec = true;
+    for (int k = 0; k < nb; k++)
+        if (!table_push<T>(tab, ptr[k], n[k], beta[k], vec)) return PDWT_EINVAL;
+    const unsigned int total = tab.chunk0[tab.nb];
+    if (total == 0) return PDWT_OK;
+    const int blocks = (int)(total < (unsigned)kMaxBlocks ? total : (unsigned)kMaxBlocks);
+    KTimer kt(K_SOFT_THRESH);
+    if (op == BL_SOFT) {
+        if (vec) hipLaunchKernelGGL((k_soft_thresh<T, true, OP_SOFT>), dim3(blocks), dim3(kUThreads), 0, stream(), tab);
+        else hipLaunchKernelGGL((k_soft_thresh<T, false, OP_SOFT>), dim3(blocks), dim3(kUThreads), 0, stream(), tab);
+    } else if (op == BL_HARD) {
+        if (vec) hipLaunchKernelGGL((k_soft_thresh<T, true, OP_HARD>), dim3(blocks), dim3(kUThreads), 0, stream(), tab);
+        else hipLaunchKernelGGL((k_soft_thresh<T, false, OP_HARD>), dim3(blocks), dim3(kUThreads), 0, stream(), tab);
+    } else {
+        return PDWT_EINVAL;
+    }
+    PDWT_CHECK_LAUNCH();
+    return PDWT_OK;
+}
+
+template <typename T>
+int band_list_abs_sum(T* const* ptr, const size_t* n, int nb, double* out)
+{
+    if (!ptr || !n || !out || nb < 1 || nb > kMaxBands) return PDWT_EINVAL;
+    BandTable<T> tab;
+    tab.nb = 0;
+    tab.chunk0[0] = 0;
+    bool vec = true;
+    for (int k = 0; k < nb; k++)
+        if (!table_push<T>(tab, ptr[k], n[k], T(0), vec)) return PDWT_EINVAL;
+    int dev = 0;
+    double* part = partials(&dev);
+    if (!part) return PDWT_ENOMEM;
+    std::lock_guard<std::mutex> red_lock(g_red_mu[dev]);  // the per-device partials are shared by every instance on that device
+    const unsigned int total = tab.chunk0[tab.nb];
+    const int blocks = (int)(total < (unsigned)kMaxBlocks ? (total ? total : 1) : (unsigned)kMaxBlocks);
+    {
+        KTimer kt(K_ABS_SUM);
+        if (vec) hipLaunchKernelGGL((k_abs_sum<T, true>), dim3(blocks), dim3(kUThreads), 0, stream(), tab, part);
+        else hipLaunchKernelGGL((k_abs_sum<T, false>), dim3(blocks), dim3(kUThreads), 0, stream(), tab, part);
+        PDWT_CHECK_LAUNCH();
+    }
+    return pdwt_memcpy_d2h(out, part + kMaxBlocks, sizeof(double));
+}
+
+template int band_list_ew<float>(int, float* const*, const size_t*, const float*, int);
+template int band_list_ew<double>(int, double* const*, const size_t*, const double*, int);
+template int band_list_abs_sum<float>(float* const*, const size_t*, int, double*);
+template int band_list_abs_sum<double>(double* const*, const size_t*, int, double*);
+}  // namespace pdwt
