@@ -365,6 +365,37 @@ int pdwt_hard_thresh3d_f64(double** d_coeffs, double beta, pdwt_info3d info, int
 int pdwt_norm1_3d_f32(float** d_coeffs, pdwt_info3d info, double* out);   /* sum |c| in double (synchronises) */
 int pdwt_norm1_3d_f64(double** d_coeffs, pdwt_info3d info, double* out);
 
+/* ---------------------------------------------------------------------------------------------
+ * 3-D stationary transform (undecimated, a-trous; the reference's do_swt with a third axis).  Same pdwt_info3d and volume
+ * layout as the 3-D DWT above.  Level j applies the 1-D a-trous level of the SWT drivers (tap spacing f = 2^(j-1)) along x,
+ * then y, then z; its input is the aaa band of level j-1.  The inverse undoes z, then y, then x.
+ * Bands: 7L+1 FULL-SIZE (Nz x Nr x Nc) bands in the order of the 3-D DWT: [A_L, then for levels L .. 1: aad, ada, add, daa, dad,
+ * dda, ddd], one zero-filled device allocation at 256-byte aligned offsets.  The inverse leaves every band intact: the
+ * intermediate approximations pass through d_image.
+ * Geometry: Nz <= 65535, Nr * Nc < 2^31, an even hlen of the bank table, and 1 <= nlevels <= ilog2(min(Nz, Nr, Nc) / (hlen - 1))
+ * (so (hlen - 1) * 2^(L-1) < min(Nz, Nr, Nc)); anything else is PDWT_EINVAL / a NULL buffer / a scratch size of 0.
+ * d_tmp: pdwt_tmp_elems_swt3d(info) elements, 4 volumes (the four x-y quadrants of a level).
+ * Kernels: pdwt_amd/csrc/swt3d.hip, two launches per level and direction (an x-y tile kernel and a z kernel).
+ * The thresholds and norm1 follow the 3-D DWT rules above with full-size bands.
+ * ------------------------------------------------------------------------------------------- */
+int pdwt_num_bands_swt3d(pdwt_info3d info);                                                    /* 7L+1, or PDWT_EINVAL */
+long long pdwt_band_size_swt3d(pdwt_info3d info, int num, int* band_Nz, int* band_Nr, int* band_Nc); /* elements, or PDWT_EINVAL */
+size_t pdwt_tmp_elems_swt3d(pdwt_info3d info);                                                 /* 0 for a bad geometry */
+float** pdwt_create_coeffs_buffer_swt3d_f32(pdwt_info3d info);
+double** pdwt_create_coeffs_buffer_swt3d_f64(pdwt_info3d info);
+int pdwt_free_coeffs_buffer_swt3d_f32(float** coeffs, pdwt_info3d info);
+int pdwt_free_coeffs_buffer_swt3d_f64(double** coeffs, pdwt_info3d info);
+int pdwt_forward3d_swt_f32(float* d_image, float** d_coeffs, float* d_tmp, pdwt_info3d info, const pdwt_filters_f32* f);
+int pdwt_forward3d_swt_f64(double* d_image, double** d_coeffs, double* d_tmp, pdwt_info3d info, const pdwt_filters_f64* f);
+int pdwt_inverse3d_swt_f32(float* d_image, float** d_coeffs, float* d_tmp, pdwt_info3d info, const pdwt_filters_f32* f);
+int pdwt_inverse3d_swt_f64(double* d_image, double** d_coeffs, double* d_tmp, pdwt_info3d info, const pdwt_filters_f64* f);
+int pdwt_soft_thresh_swt3d_f32(float** d_coeffs, float beta, pdwt_info3d info, int do_thresh_appcoeffs, int normalize);
+int pdwt_soft_thresh_swt3d_f64(double** d_coeffs, double beta, pdwt_info3d info, int do_thresh_appcoeffs, int normalize);
+int pdwt_hard_thresh_swt3d_f32(float** d_coeffs, float beta, pdwt_info3d info, int do_thresh_appcoeffs, int normalize);
+int pdwt_hard_thresh_swt3d_f64(double** d_coeffs, double beta, pdwt_info3d info, int do_thresh_appcoeffs, int normalize);
+int pdwt_norm1_swt3d_f32(float** d_coeffs, pdwt_info3d info, double* out);   /* sum |c| in double (synchronises) */
+int pdwt_norm1_swt3d_f64(double** d_coeffs, pdwt_info3d info, double* out);
+
 #ifdef __cplusplus
 }
 #endif

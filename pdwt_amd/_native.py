@@ -48,13 +48,15 @@ PLAIN_SYMBOLS = ["pdwt_device_count", "pdwt_set_device", "pdwt_get_device", "pdw
                  "pdwt_graph_destroy", "pdwt_num_wavelets", "pdwt_wavelet_name", "pdwt_num_bands", "pdwt_band_size", "pdwt_tmp_elems", "pdwt_debug_set", "pdwt_debug_get", "pdwt_clock_probe_enable", "pdwt_clock_probe_read", "pdwt_clock_probe_dump", "pdwt_probe_bandwidth", "pdwt_selfcheck_vmcnt_order", "pdwt_rccl_available", "pdwt_rccl_allreduce_sum_f64", "pdwt_sum_result_index", "pdwt_sum_spare_index",
                  "pdwt_batch2d_create_f32", "pdwt_batch2d_forward_f32", "pdwt_batch2d_inverse_f32", "pdwt_batch2d_destroy",
                  "pdwt_batch2d_create_f64", "pdwt_batch2d_forward_f64", "pdwt_batch2d_inverse_f64", "pdwt_batch2d_destroy_f64",
-                 "pdwt_sum_scratch_doubles", "pdwt_sum_scratch_read", "pdwt_num_bands3d", "pdwt_band_size3d", "pdwt_tmp_elems3d"]
+                 "pdwt_sum_scratch_doubles", "pdwt_sum_scratch_read", "pdwt_num_bands3d", "pdwt_band_size3d", "pdwt_tmp_elems3d",
+                 "pdwt_num_bands_swt3d", "pdwt_band_size_swt3d", "pdwt_tmp_elems_swt3d"]
 TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coeffs_buffer", "copy_coeffs_buffer",
                   "soft_thresh", "soft_thresh_sum", "norm1", "norm1_as_double", "norm1_enqueue", "hard_thresh", "proj_linf", "shrink", "group_soft_thresh",
                   "norm2sq", "norm2sq_as_double", "add_coeffs", "circshift", "forward_nonseparable", "inverse_nonseparable",
                   "forward_swt_nonseparable", "inverse_swt_nonseparable",
                   "create_coeffs_buffer3d", "free_coeffs_buffer3d", "forward3d_separable", "inverse3d_separable", "soft_thresh3d", "hard_thresh3d",
-                  "norm1_3d"] + DRIVERS + HAAR_DRIVERS)
+                  "norm1_3d", "create_coeffs_buffer_swt3d", "free_coeffs_buffer_swt3d", "forward3d_swt", "inverse3d_swt",
+                  "soft_thresh_swt3d", "hard_thresh_swt3d", "norm1_swt3d"] + DRIVERS + HAAR_DRIVERS)
 
 _hip = None
 _host = {}
@@ -125,6 +127,11 @@ def hip():
     L.pdwt_band_size3d.argtypes = [Info3D, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     L.pdwt_tmp_elems3d.restype = sz
     L.pdwt_tmp_elems3d.argtypes = [Info3D]
+    L.pdwt_num_bands_swt3d.argtypes = [Info3D]
+    L.pdwt_band_size_swt3d.restype = C.c_longlong
+    L.pdwt_band_size_swt3d.argtypes = [Info3D, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+    L.pdwt_tmp_elems_swt3d.restype = sz
+    L.pdwt_tmp_elems_swt3d.argtypes = [Info3D]
     for sfx, ct, FT in (("f32", C.c_float, Filters32), ("f64", C.c_double, Filters64)):
         P = C.POINTER(ct)
         PP = C.POINTER(P)
@@ -161,6 +168,15 @@ def hip():
         for d in ("soft_thresh3d", "hard_thresh3d"):
             getattr(L, "pdwt_%s_%s" % (d, sfx)).argtypes = [PP, ct, Info3D, ci, ci]
         getattr(L, "pdwt_norm1_3d_" + sfx).argtypes = [PP, Info3D, C.POINTER(C.c_double)]
+        f = getattr(L, "pdwt_create_coeffs_buffer_swt3d_" + sfx)
+        f.restype = PP
+        f.argtypes = [Info3D]
+        getattr(L, "pdwt_free_coeffs_buffer_swt3d_" + sfx).argtypes = [PP, Info3D]
+        for d in ("forward3d_swt", "inverse3d_swt"):
+            getattr(L, "pdwt_%s_%s" % (d, sfx)).argtypes = [vp, PP, vp, Info3D, C.POINTER(FT)]
+        for d in ("soft_thresh_swt3d", "hard_thresh_swt3d"):
+            getattr(L, "pdwt_%s_%s" % (d, sfx)).argtypes = [PP, ct, Info3D, ci, ci]
+        getattr(L, "pdwt_norm1_swt3d_" + sfx).argtypes = [PP, Info3D, C.POINTER(C.c_double)]
     _hip = L
     return L
 
@@ -224,28 +240,29 @@ def host(dtype):
             getattr(L, "pdwt_images_" + n).argtypes = [vp]
         L.pdwt_wavelets_coeff_int_ptr.restype = C.c_ssize_t
         L.pdwt_wavelets_coeff_int_ptr.argtypes = [vp, ci]
-        # Wavelets3D (include/wt3d.h, wt3d.cpp)
-        L.pdwt_wavelets3d_new.restype = vp
-        L.pdwt_wavelets3d_new.argtypes = [vp, ci, ci, ci, C.c_char_p, ci, ci]
-        for n in ("delete", "forward", "inverse", "num_bands", "state"):
-            getattr(L, "pdwt_wavelets3d_" + n).argtypes = [vp]
-        for n in ("soft_threshold", "hard_threshold"):
-            getattr(L, "pdwt_wavelets3d_" + n).argtypes = [vp, ct, ci, ci]
-        L.pdwt_wavelets3d_norm1.restype = ct
-        L.pdwt_wavelets3d_norm1.argtypes = [vp]
-        L.pdwt_wavelets3d_norm1_f64.restype = C.c_double
-        L.pdwt_wavelets3d_norm1_f64.argtypes = [vp]
-        L.pdwt_wavelets3d_get_image.argtypes = [vp, vp]
-        L.pdwt_wavelets3d_set_image.argtypes = [vp, vp, ci]
-        L.pdwt_wavelets3d_band_shape.restype = C.c_longlong
-        L.pdwt_wavelets3d_band_shape.argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
-        L.pdwt_wavelets3d_get_coeff.argtypes = [vp, vp, ci]
-        L.pdwt_wavelets3d_set_coeff.argtypes = [vp, vp, ci, ci]
-        L.pdwt_wavelets3d_info.argtypes = [vp, C.POINTER(Info3D)]
-        L.pdwt_wavelets3d_image_int_ptr.restype = C.c_ssize_t
-        L.pdwt_wavelets3d_image_int_ptr.argtypes = [vp]
-        L.pdwt_wavelets3d_coeff_int_ptr.restype = C.c_ssize_t
-        L.pdwt_wavelets3d_coeff_int_ptr.argtypes = [vp, ci]
+        # Wavelets3D (include/wt3d.h, wt3d.cpp) and StationaryWavelets3D (include/swt3d.h, swt3d.cpp): the same handle API
+        for pfx in ("pdwt_wavelets3d_", "pdwt_swt3d_"):
+            getattr(L, pfx + "new").restype = vp
+            getattr(L, pfx + "new").argtypes = [vp, ci, ci, ci, C.c_char_p, ci, ci]
+            for n in ("delete", "forward", "inverse", "num_bands", "state"):
+                getattr(L, pfx + n).argtypes = [vp]
+            for n in ("soft_threshold", "hard_threshold"):
+                getattr(L, pfx + n).argtypes = [vp, ct, ci, ci]
+            getattr(L, pfx + "norm1").restype = ct
+            getattr(L, pfx + "norm1").argtypes = [vp]
+            getattr(L, pfx + "norm1_f64").restype = C.c_double
+            getattr(L, pfx + "norm1_f64").argtypes = [vp]
+            getattr(L, pfx + "get_image").argtypes = [vp, vp]
+            getattr(L, pfx + "set_image").argtypes = [vp, vp, ci]
+            getattr(L, pfx + "band_shape").restype = C.c_longlong
+            getattr(L, pfx + "band_shape").argtypes = [vp, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+            getattr(L, pfx + "get_coeff").argtypes = [vp, vp, ci]
+            getattr(L, pfx + "set_coeff").argtypes = [vp, vp, ci, ci]
+            getattr(L, pfx + "info").argtypes = [vp, C.POINTER(Info3D)]
+            getattr(L, pfx + "image_int_ptr").restype = C.c_ssize_t
+            getattr(L, pfx + "image_int_ptr").argtypes = [vp]
+            getattr(L, pfx + "coeff_int_ptr").restype = C.c_ssize_t
+            getattr(L, pfx + "coeff_int_ptr").argtypes = [vp, ci]
         _host[dt] = L
     return _host[dt]
 
