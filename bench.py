@@ -11,11 +11,17 @@ independent, so every rank transforms its own image -- no data-path collective -
 throughput is N images per step ("scaling": "weak").  RCCL is used only for the barriers and the
 max-over-ranks of the elapsed time.
 
-Extra objects in the JSON line:
+A plain run does only what the headline needs: set-up, the untimed settle phase and the W warm-up steps, the K timed steps,
+--dump-outputs if given, and one JSON line with the headline fields (metric, value, unit, higher_is_better, dtype, ms_per_step,
+and the run's shape).  --full measures and checks everything else as well, after the same timed steps, in the same process:
+  gpu_ms_per_step, steady_state  the K steps again between two HIP events; the step repeated over >= 0.1 s when K steps are short.
+  sanity        a fresh forward+inverse against the input; norm1() against torch (configs with the extra operators); the
+                norm1 all-reduce of the N > 1 path.
   roofline      dominant kernel: algorithmic bytes of its launches / their HIP-event duration
-                (events recorded on the library stream by pdwt_ktime_*), vs 8000 GB/s.
+                (events recorded on the library stream by pdwt_ktime_*), vs 8000 GB/s, and the copy rate of the same volume.
   cpu_baseline  the CPU oracle (plain-C restatement, OpenMP) timed on this host's cores on a
                 bounded sample of the same workload (rank 0, N = 1 only).
+  power, clock_probe, extra_timing, other_configs (N = 1) / streaming_runs (N > 1), collective, per_rank.
 
 --dump-outputs DIR writes what the last timed step of --config handed its caller (the reconstructed
 image(s), plus the value norm1() returned in c5) as DIR/<name>.npy, <= 64 MB in all (a fixed sample
@@ -258,9 +264,10 @@ def pick_dominant(cfg, kernels, per_kernel_bytes, levels_eff):
     return dom, per_kernel_bytes[dom]
 
 
-def run_config(name, args, L, torch, dist, rank, world, steps, warmup, settle_ms, cpu_seconds, do_roofline, dump_dir=None):
+def run_config(name, args, L, torch, dist, rank, world, steps, warmup, settle_ms, cpu_seconds, do_roofline, dump_dir=None, full=True):
     """Time `steps` steps of config `name` on this rank's GPU; returns the fields of the JSON line for it.  `dump_dir`: write what the
-    last timed step computed there (dump_outputs)."""
+    last timed step computed there (dump_outputs).  `full` False: return right after the timed steps (and the dump) with the headline
+    fields only."""
     import numpy as np
     cfg = CONFIGS[name]
 
@@ -368,7 +375,6 @@ def run_config(name, args, L, torch, dist, rank, world, steps, warmup, settle_ms
     barrier()
     elapsed = time.perf_counter() - t0
     wall1 = time.time()
-    power = _SAMPLER.window(wall0, wall1) if _SAMPLER is not None else None
     if dump_dir is not None:
         # what a caller of the step holds afterwards: the reconstructed image(s) -- inverse() leaves the bands meaningless (W_INVERSE) --
         # and, in the configs with the extra operators, the value norm1() returned
@@ -378,6 +384,20 @@ def run_config(name, args, L, torch, dist, rank, world, steps, warmup, settle_ms
         if cfg["extra"]:
             outs.append((pre + "norm1", np.array([last_norm1[0]], dtype=np.float64)))
         dump_outputs(dump_dir, outs, DUMP_BYTES // world)
+    if world > 1:
+        t = torch.tensor([elapsed], device="cuda" if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    pixels = cfg["Nr"] * cfg["Nc"] * nbatch
+    ms_per_step = elapsed / steps * 1e3
+    value = world * pixels / (elapsed / steps) / 1e6
+    head = {"value": round(value, 1), "unit": cfg["unit"], "ms_per_step": round(ms_per_step, 5), "steps": steps, "warmup": warmup,
+            "levels": levels_eff, "workload": cfg["desc"], "dtype": "f32" if cfg["dtype"] == "float32" else "f64",
+            "images_per_step": nbatch, "ms_per_image_pair": round(ms_per_step / nbatch, 5)}
+    if not full:
+        return head
+
+    power = _SAMPLER.window(wall0, wall1) if _SAMPLER is not None else None
     # the same K steps once more between two HIP events on the library stream: `gpu_ms_per_step` (what the GPU spent between the first
     # kernel's start and the last one's end, without the bracket)
     sync()
@@ -402,10 +422,6 @@ def run_config(name, args, L, torch, dist, rank, world, steps, warmup, settle_ms
         torch.cuda.synchronize()
         steady = {"steps": n_long, "ms_per_step": round((time.perf_counter() - t0s) / n_long * 1e3, 5),
                   "what": "the same step, same bracket, over a region long enough to amortise the bracket (first launch on an idle GPU + synchronize wake-up) and the cold start; not used for `value`"}
-    if world > 1:
-        t = torch.tensor([elapsed], device="cuda" if dist.get_backend() == "nccl" else "cpu", dtype=torch.float64)
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed = float(t.item())
 
     # sanity of the timed work (untimed): pixels really go through.  Every config: one fresh forward+inverse reproduces the
     # input.  Configs with the extra operators: norm1() against a float64 sum over the bands taken by torch on the GPU
@@ -444,9 +460,6 @@ def run_config(name, args, L, torch, dist, rank, world, steps, warmup, settle_ms
         sanity["norm1_ranks"] = len(parts)
         W.inverse()
 
-    pixels = cfg["Nr"] * cfg["Nc"] * nbatch
-    ms_per_step = elapsed / steps * 1e3
-    value = world * pixels / (elapsed / steps) / 1e6
     step_bytes, per_kernel_bytes = algorithmic_bytes(cfg, levels_eff)
     step_bytes *= nbatch
     per_kernel_bytes = {k: v * nbatch for k, v in per_kernel_bytes.items()}
@@ -647,11 +660,9 @@ def run_config(name, args, L, torch, dist, rank, world, steps, warmup, settle_ms
         cpu = cpu_baseline(cfg, cpu_seconds)
     del W
     del Ws
-    return {"value": round(value, 1), "unit": cfg["unit"], "ms_per_step": round(ms_per_step, 5), "gpu_ms_per_step": round(gpu_ms / steps, 5),
-            "steps": steps, "warmup": warmup, "levels": levels_eff, "workload": cfg["desc"], "dtype": "f32" if cfg["dtype"] == "float32" else "f64",
-            "sanity": sanity, "roundtrip_max_rel_err": rt_err, "roofline": roofline, "cpu_baseline": cpu, "power": power,
-            "images_per_step": nbatch, "ms_per_image_pair": round(ms_per_step / nbatch, 5), "extra_timing": extra_timing, "clock_probe": clock_probe, "steady_state": steady,
-            "kernels": {k: {a: round(b, 3) for a, b in v.items()} for k, v in kernels.items()}}
+    return dict(head, gpu_ms_per_step=round(gpu_ms / steps, 5), sanity=sanity, roundtrip_max_rel_err=rt_err, roofline=roofline, cpu_baseline=cpu,
+                power=power, extra_timing=extra_timing, clock_probe=clock_probe, steady_state=steady,
+                kernels={k: {a: round(b, 3) for a, b in v.items()} for k, v in kernels.items()})
 
 
 # ---------------------------------------------------------------------------------------------------------------------
@@ -791,9 +802,11 @@ def main():
     ap.add_argument("--steps", type=int, default=2000)  # >= ~0.1 s of GPU work: the clocks need ~50 ms of load to settle
     ap.add_argument("--warmup", type=int, default=200)
     ap.add_argument("--config", default="c2", choices=sorted(CONFIGS))
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the cpu_baseline leg (0 = skip)")
-    ap.add_argument("--no-roofline", action="store_true")
-    ap.add_argument("--no-others", action="store_true", help="skip the short runs of the other configs (other_configs)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, measure and check everything else too (roofline, sanity, cpu_baseline, power, other configs, ...)")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="--full: budget of the cpu_baseline leg (0 = skip)")
+    ap.add_argument("--no-roofline", action="store_true", help="--full: skip the per-kernel pass (roofline, kernels)")
+    ap.add_argument("--no-others", action="store_true", help="--full: skip the short runs of the other configs (other_configs, streaming_runs)")
     ap.add_argument("--batch-instances", action="store_true", help="c2_batch: cycle 16 private Wavelets instances (one image per launch) instead of the ImageBatch entry")
     ap.add_argument("--settle-ms", type=float, default=150.0, help="untimed load before the warm-up steps (clock settling)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -837,24 +850,25 @@ def main():
             dist.init_process_group("nccl", rank=rank, world_size=world, device_id=torch.device("cuda", local_rank))
 
     global _SAMPLER
-    # every rank samples the clock and socket power of ITS device (N > 1: eight GPUs drawing power at once is what a scaling run is about);
-    # with all ranks on device 0 (PDWT_BENCH_ONE_GPU) rank 0 alone samples it
-    _SAMPLER = PowerSampler(local_rank) if os.environ.get("PDWT_BENCH_ONE_GPU") != "1" or rank == 0 else None
-    time.sleep(0.5)  # (the helper imports amdsmi)
-    # the size of the collective group, from the communicator itself: an all-reduce of one 1 per rank over the backend the batch split uses
     rccl_ranks, coll_backend = None, None
-    if world > 1:
-        coll_backend = dist.get_backend()
-        one = torch.ones(1, device="cuda" if coll_backend == "nccl" else "cpu", dtype=torch.float64)
-        dist.all_reduce(one)
-        rccl_ranks = int(round(float(one.item())))
+    if args.full:
+        # every rank samples the clock and socket power of ITS device (N > 1: eight GPUs drawing power at once is what a scaling run is about);
+        # with all ranks on device 0 (PDWT_BENCH_ONE_GPU) rank 0 alone samples it
+        _SAMPLER = PowerSampler(local_rank) if os.environ.get("PDWT_BENCH_ONE_GPU") != "1" or rank == 0 else None
+        time.sleep(0.5)  # (the helper imports amdsmi)
+        # the size of the collective group, from the communicator itself: an all-reduce of one 1 per rank over the backend the batch split uses
+        if world > 1:
+            coll_backend = dist.get_backend()
+            one = torch.ones(1, device="cuda" if coll_backend == "nccl" else "cpu", dtype=torch.float64)
+            dist.all_reduce(one)
+            rccl_ranks = int(round(float(one.item())))
     cfg = CONFIGS[args.config]
     res = run_config(args.config, args, L, torch, dist, rank, world, args.steps, args.warmup, args.settle_ms, args.cpu_seconds, not args.no_roofline,
-                     dump_dir=args.dump_outputs)
+                     dump_dir=args.dump_outputs, full=args.full)
 
     # The other BASELINE configs, short runs in the same process (N = 1 only; the headline fields above stay those of --config)
     others = None
-    if world == 1 and not args.no_others and args.config == "c2":
+    if args.full and world == 1 and not args.no_others and args.config == "c2":
         others = {}
         for name, (st, wu, settle, cpu_s) in OTHER_RUNS.items():
             try:
@@ -867,7 +881,7 @@ def main():
     # at once.  Every rank therefore also times, briefly, the two workloads that DO stream: c2_batch (16 distinct images per GPU through the
     # batched entry) and its C4 shard (8192 x 8192 rows of the batched-1D array) -- whole-job values, max over ranks, like the headline.
     streaming = None
-    if world > 1 and not args.no_others and args.config == "c2":
+    if args.full and world > 1 and not args.no_others and args.config == "c2":
         streaming = {}
         for name in ("c2_batch", "c4"):
             st, wu, settle, _ = OTHER_RUNS[name]
@@ -879,7 +893,7 @@ def main():
             torch.cuda.empty_cache()
     # per-rank clock / power means of the headline's timed region, gathered as numbers
     per_rank = None
-    if world > 1:
+    if args.full and world > 1:
         pw = res.get("power") or {}
         mine = torch.tensor([float((pw.get("sclk_mhz") or {}).get("mean") or -1.0), float((pw.get("socket_w") or {}).get("mean") or -1.0)],
                             device="cuda" if coll_backend == "nccl" else "cpu", dtype=torch.float64)
@@ -898,14 +912,18 @@ def main():
             "config": {"workload": cfg["desc"], "images_per_gpu_per_step": res["images_per_step"], "levels": res["levels"],
                        "parallelism": "batch-split x%d (no data-path collective)" % world,
                        "working_set": ("one image per GPU, transformed over and over: its ~170 MB stay in the 256 MiB Infinity Cache; the same workload on a "
-                                       "batch that streams through HBM is other_configs.c2_batch") if args.config == "c2" else None},
-            "gpu_ms_per_step": res["gpu_ms_per_step"], "settle_ms": args.settle_ms, "roundtrip_max_rel_err": res["roundtrip_max_rel_err"],
+                                       "batch that streams through HBM is other_configs.c2_batch of a --full run") if args.config == "c2" else None},
+            "settle_ms": args.settle_ms,
+        }
+    if rank == 0 and args.full:
+        line.update({
+            "gpu_ms_per_step": res["gpu_ms_per_step"], "roundtrip_max_rel_err": res["roundtrip_max_rel_err"],
             "sanity": res["sanity"], "roofline": res["roofline"], "cpu_baseline": res["cpu_baseline"], "power": res["power"],
             "extra_timing": res.get("extra_timing"), "clock_probe": res.get("clock_probe"), "steady_state": res.get("steady_state"),
             "kernels": res["kernels"], "other_configs": others,
             "rccl_ranks": rccl_ranks if coll_backend == "nccl" else None, "collective": {"backend": coll_backend, "ranks": rccl_ranks} if world > 1 else None,
             "per_rank": per_rank,
-        }
+        })
         # the HBM-streaming throughputs next to the cache-resident headline, at every N: whole-job Mpixels/s of 16 distinct images per GPU
         # through the batched entry, and whole-job Msamples/s of the C4 shards (N = 1: the same numbers as other_configs.c2_batch / .c4)
         src = (streaming if world > 1 else others) or {}
@@ -927,6 +945,7 @@ def main():
                 "ms_per_image_pair": cb.get("ms_per_image_pair"), "Mpixels_per_s": cb.get("value"),
                 "step_frac_of_peak": rb.get("step_frac_of_peak"), "kernel": rb.get("kernel"), "achieved": rb.get("achieved"), "frac": rb.get("frac"),
                 "avg_launch_us": rb.get("avg_launch_us"), "copy_ceiling": rb.get("copy_ceiling")}
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if _SAMPLER is not None:
         _SAMPLER.close()

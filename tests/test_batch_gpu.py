@@ -168,7 +168,7 @@ def test_bench_two_ranks_code_path_on_one_gpu():
     import subprocess
     env = dict(os.environ, PDWT_BENCH_ONE_GPU="1", PDWT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
-                        "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5",
+                        "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full",
                         "--cpu-seconds", "0", "--settle-ms", "20"], capture_output=True, text=True, timeout=580, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -196,7 +196,7 @@ def test_bench_plain_form_starts_its_own_ranks():
     env = dict(os.environ, PDWT_BENCH_ONE_GPU="1", PDWT_BENCH_BACKEND="gloo")
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--cpu-seconds", "0",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "0",
                         "--settle-ms", "20", "--no-others"], capture_output=True, text=True, timeout=580, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
@@ -213,7 +213,7 @@ def test_bench_line_kernel_times_fit_the_timed_step():
     `ms_per_step`, the per-kernel pass states its own duration, and `roofline.achieved` follows from the dominant kernel's timed share."""
     import json
     import subprocess
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--cpu-seconds", "0", "--settle-ms", "50"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "20", "--warmup", "5", "--full", "--cpu-seconds", "0", "--settle-ms", "50"],
                        capture_output=True, text=True, timeout=880, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     d = json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1])
@@ -273,7 +273,7 @@ def test_bench_four_ranks_c4_code_path_on_one_gpu():
     env = dict(os.environ, PDWT_BENCH_ONE_GPU="1", PDWT_BENCH_BACKEND="gloo", MASTER_ADDR="127.0.0.1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
                         "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--config", "c4", "--gpus", "4", "--steps", "10", "--warmup", "3",
-                        "--cpu-seconds", "0", "--settle-ms", "20", "--no-roofline"], capture_output=True, text=True, timeout=880, env=env, cwd=ROOT)
+                        "--full", "--cpu-seconds", "0", "--settle-ms", "20", "--no-roofline"], capture_output=True, text=True, timeout=880, env=env, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-2000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, r.stdout[-2000:]

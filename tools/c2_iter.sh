@@ -8,7 +8,7 @@ fi
 [ $# -eq 0 ] && set -- ""
 for V in "$@"; do
   echo "== [$V]"
-  env $V python bench.py --config ${CONFIG:-c2} --steps ${STEPS:-1000} --warmup 100 --cpu-seconds 0 --no-others 2>&1 | tail -1 | python -c "
+  env $V python bench.py --config ${CONFIG:-c2} --steps ${STEPS:-1000} --warmup 100 --full --cpu-seconds 0 --no-others 2>&1 | tail -1 | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); r=d['roofline']
 print('value %.0f  us/step %.2f (gpu %.2f)  dom %s %.0f GB/s frac %.3f  stepfrac %.3f  rt %.1e' % (d['value'], d['ms_per_step']*1e3, d['gpu_ms_per_step']*1e3, r['kernel'], r['achieved'], r['frac'], r['step_frac_of_peak'], d['roundtrip_max_rel_err']))

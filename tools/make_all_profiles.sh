@@ -31,9 +31,9 @@ if echo "$CFGS" | grep -qw c2; then
   cd /tmp && export TMPDIR=/tmp
   # the same workload streaming through HBM: 16 images per step through the batched entry
   D=$R/gpurun_out/prof_${TAG}_c2_batch_kt; rm -rf $D
-  timeout 400 rocprofv3 --kernel-trace --stats -d $D -o t --output-format csv -- python $R/bench.py --config c2_batch --steps 40 --warmup 10 --cpu-seconds 0 --no-others > $D.log 2>&1
+  timeout 400 rocprofv3 --kernel-trace --stats -d $D -o t --output-format csv -- python $R/bench.py --config c2_batch --steps 40 --warmup 10 --full --cpu-seconds 0 --no-others > $D.log 2>&1
   grep '^{' $D.log | tail -1 > $OUT/${TAG}_c2_batch_bench_line.json
-  python $R/tools/summarize_profile.py $D $OUT/${TAG}_c2_batch_kernel_trace.md "${TAG}, config c2_batch: rocprofv3 --kernel-trace --stats -- python bench.py --config c2_batch --steps 40 --warmup 10 --cpu-seconds 0 --no-others"
+  python $R/tools/summarize_profile.py $D $OUT/${TAG}_c2_batch_kernel_trace.md "${TAG}, config c2_batch: rocprofv3 --kernel-trace --stats -- python bench.py --config c2_batch --steps 40 --warmup 10 --full --cpu-seconds 0 --no-others"
   for SET in "SQ_BUSY_CYCLES SQ_WAVES SQ_INSTS_VALU SQ_INSTS_SALU" "SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_INST_CYCLES_SALU SQ_WAVE_CYCLES" "SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_INSTS_LDS SQ_WAIT_ANY"; do
     N=$(echo $SET | cut -d' ' -f1)
     D=$R/gpurun_out/pmc_${TAG}_c2_$N; rm -rf $D

@@ -8,9 +8,9 @@ R=$PWD; export PYTHONPATH=$R
 OUT=$R/gpurun_out/profiles_$TAG; mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 D=$R/gpurun_out/prof_${TAG}_${CFG}_kt; rm -rf $D
-timeout 400 rocprofv3 --kernel-trace --stats -d $D -o t --output-format csv -- python $R/bench.py --config $CFG --steps 500 --warmup 100 --cpu-seconds 0 --no-others > $D.log 2>&1
+timeout 400 rocprofv3 --kernel-trace --stats -d $D -o t --output-format csv -- python $R/bench.py --config $CFG --steps 500 --warmup 100 --full --cpu-seconds 0 --no-others > $D.log 2>&1
 grep '^{' $D.log | tail -1 > $OUT/${TAG}_${CFG}_bench_line.json
-python $R/tools/summarize_profile.py $D $OUT/${TAG}_${CFG}_kernel_trace.md "${TAG}, config ${CFG}: rocprofv3 --kernel-trace --stats -- python bench.py --config ${CFG} --steps 500 --warmup 100 --cpu-seconds 0 --no-others"
+python $R/tools/summarize_profile.py $D $OUT/${TAG}_${CFG}_kernel_trace.md "${TAG}, config ${CFG}: rocprofv3 --kernel-trace --stats -- python bench.py --config ${CFG} --steps 500 --warmup 100 --full --cpu-seconds 0 --no-others"
 [ "$PMC" = "1" ] || { cd $R; ls $OUT; exit 0; }
 for C in FETCH_SIZE WRITE_SIZE; do
   D=$R/gpurun_out/pmc_${TAG}_${CFG}_$C; rm -rf $D
