@@ -396,6 +396,30 @@ int pdwt_hard_thresh_swt3d_f64(double** d_coeffs, double beta, pdwt_info3d info,
 int pdwt_norm1_swt3d_f32(float** d_coeffs, pdwt_info3d info, double* out);   /* sum |c| in double (synchronises) */
 int pdwt_norm1_swt3d_f64(double** d_coeffs, pdwt_info3d info, double* out);
 
+/* -----------------------------------------------------------------------------------------------
+ * Band statistics and one threshold per band, over an explicit list of bands: band k is d_ptr[k] with n[k] elements,
+ * 1 <= nb <= 97 (the classes of wt.h / wt3d.h / swt3d.h build the list from their geometry).  Kernels: pdwt_amd/csrc/bandstats.hip.
+ *
+ * The stats entries fill out[k] for every band: n, sum |c|, sum c^2 and max |c| (accumulated in double; one launch for all
+ * bands; bit-reproducible: no float atomics) and, where want_median[k] != 0, the exact median of |c| -- the mean of the
+ * elements of rank (n-1)/2 and n/2, found by radix select (3 read passes of the asking bands in float, 6 in double) --
+ * otherwise NaN.  want_median[k] == 2 asks for the median alone: band k is left out of the moments launch and its sums and max are
+ * NaN.  want_median == NULL asks for no median.  n[k] == 0 gives zeros and a NaN median.  A NaN element orders
+ * above +inf in the selection.  They SYNCHRONISE (one copy to the host at the end, like the norm1 entries) and so must not
+ * be called between the begin and the end of a graph capture.
+ *
+ * The thresh entries apply op (0 soft, 1 hard) with beta[k] to band k, in place, in one launch; beta[k] < 0 leaves band k
+ * alone.  Asynchronous, like the soft-threshold entries above.
+ * nb < 1, nb > 97, a NULL d_ptr / n / out / beta or an unknown op: PDWT_EINVAL.
+ * --------------------------------------------------------------------------------------------- */
+typedef struct pdwt_band_stats {
+    double n, sum_abs, sum_sq, max_abs, median_abs;
+} pdwt_band_stats;
+int pdwt_bandlist_stats_f32(const float* const* d_ptr, const size_t* n, int nb, const unsigned char* want_median, pdwt_band_stats* out);
+int pdwt_bandlist_stats_f64(const double* const* d_ptr, const size_t* n, int nb, const unsigned char* want_median, pdwt_band_stats* out);
+int pdwt_bandlist_thresh_f32(int op, float* const* d_ptr, const size_t* n, const float* beta, int nb);
+int pdwt_bandlist_thresh_f64(int op, double* const* d_ptr, const size_t* n, const double* beta, int nb);
+
 #ifdef __cplusplus
 }
 #endif

@@ -65,6 +65,11 @@ typedef enum w_state {
     W_THRESHOLD_ERROR  /* a threshold launch failed */
 } w_state;
 
+/* ADDITION: statistics of one band (band_stats / all_band_stats below); median_abs is NaN when it was not asked for */
+struct w_band_stats {
+    double n, sum_abs, sum_sq, max_abs, median_abs;
+};
+
 class Wavelets {
   public:
     /* data members: order and types of src/wt.h:24-34 */
@@ -128,6 +133,23 @@ class Wavelets {
     /* ADDITION: 1 once set_filters_forward() / set_filters_inverse() has replaced the bank of `wname` (wt_batch.h: a batch whose
      * members do not all run the named bank any more is transformed image by image) */
     int custom_filters() const;
+    /* ADDITIONS: band statistics and noise-adaptive thresholds, computed on the device (pdwt_amd/csrc/bandstats.hip).  All five need
+     * valid coefficients (after forward(), before inverse()); otherwise band_stats / all_band_stats return a negative value,
+     * estimate_sigma / denoise return -1, threshold_bands does nothing, and nothing is launched.
+     *   band_stats       n, sum |c|, sum c^2, max |c| (accumulated in double) and, with_median, the exact median of |c| of band num
+     *   all_band_stats   the same for every band (out: 3L+1 / L+1 entries) in ONE moments launch
+     *   estimate_sigma   median |finest diagonal band| / 0.6744897501960817  (band 3 = D1 in 2-D; band 1 = D1 of a batched 1-D instance, all rows together)
+     *   threshold_bands  one beta per band (3L+1 / L+1 betas); beta < 0 leaves the band alone; kind 0 soft, 1 hard
+     *   denoise          method 0 VisuShrink: every detail band gets sigma * sqrt(2 ln N), N = Nr*Nc (Nc for batched 1-D);
+     *                    method 1 BayesShrink: detail band b gets sigma^2 / sqrt(ms_b - sigma^2), ms_b = sum c^2 / n, or max |c| (the band
+     *                    goes to zero) when ms_b <= sigma^2.  sigma < 0: estimate_sigma().  Band 0 is never touched (beta -1).  Host
+     *                    arithmetic in double, betas rounded to DTYPE once and returned in betas_out (3L+1 / L+1 entries) when given.
+     *                    Returns the sigma it used.  The rules assume an orthonormal bank; bior / rbio banks get them as they are. */
+    int band_stats(int num, w_band_stats* out, int with_median = 1);
+    int all_band_stats(w_band_stats* out, int with_median = 0);
+    double estimate_sigma();
+    void threshold_bands(const DTYPE* betas, int kind = 0);
+    double denoise(int method, double sigma = -1.0, int kind = 0, DTYPE* betas_out = NULL);
 
   private:
     /* per-instance filter bank (the reference keeps it in process-global constant memory, so two

@@ -18,6 +18,14 @@ class Info3D(C.Structure):
     _fields_ = [("Nz", C.c_int), ("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int)]
 
 
+class BandStats(C.Structure):
+    """== pdwt_band_stats (include/pdwt_hip.h) == w_band_stats (include/wt.h)."""
+    _fields_ = [("n", C.c_double), ("sum_abs", C.c_double), ("sum_sq", C.c_double), ("max_abs", C.c_double), ("median_abs", C.c_double)]
+
+    def as_dict(self):
+        return {k: float(getattr(self, k)) for k, _ in self._fields_}
+
+
 class Info(C.Structure):
     """== pdwt_info (include/pdwt_hip.h) == reference w_info (src/utils.h:9-19)."""
     _fields_ = [("ndims", C.c_int), ("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("do_swt", C.c_int), ("hlen", C.c_int)]
@@ -56,7 +64,7 @@ TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coe
                   "forward_swt_nonseparable", "inverse_swt_nonseparable",
                   "create_coeffs_buffer3d", "free_coeffs_buffer3d", "forward3d_separable", "inverse3d_separable", "soft_thresh3d", "hard_thresh3d",
                   "norm1_3d", "create_coeffs_buffer_swt3d", "free_coeffs_buffer_swt3d", "forward3d_swt", "inverse3d_swt",
-                  "soft_thresh_swt3d", "hard_thresh_swt3d", "norm1_swt3d"] + DRIVERS + HAAR_DRIVERS)
+                  "soft_thresh_swt3d", "hard_thresh_swt3d", "norm1_swt3d", "bandlist_stats", "bandlist_thresh"] + DRIVERS + HAAR_DRIVERS)
 
 _hip = None
 _host = {}
@@ -177,6 +185,8 @@ def hip():
         for d in ("soft_thresh_swt3d", "hard_thresh_swt3d"):
             getattr(L, "pdwt_%s_%s" % (d, sfx)).argtypes = [PP, ct, Info3D, ci, ci]
         getattr(L, "pdwt_norm1_swt3d_" + sfx).argtypes = [PP, Info3D, C.POINTER(C.c_double)]
+        getattr(L, "pdwt_bandlist_stats_" + sfx).argtypes = [PP, C.POINTER(sz), ci, C.POINTER(C.c_ubyte), C.POINTER(BandStats)]
+        getattr(L, "pdwt_bandlist_thresh_" + sfx).argtypes = [ci, PP, C.POINTER(sz), P, ci]
     _hip = L
     return L
 
@@ -263,6 +273,15 @@ def host(dtype):
             getattr(L, pfx + "image_int_ptr").argtypes = [vp]
             getattr(L, pfx + "coeff_int_ptr").restype = C.c_ssize_t
             getattr(L, pfx + "coeff_int_ptr").argtypes = [vp, ci]
+        # band statistics and noise-adaptive thresholds: the same five handle functions on the three classes
+        for pfx in ("pdwt_wavelets_", "pdwt_wavelets3d_", "pdwt_swt3d_"):
+            getattr(L, pfx + "band_stats").argtypes = [vp, ci, C.POINTER(BandStats), ci]
+            getattr(L, pfx + "all_band_stats").argtypes = [vp, C.POINTER(BandStats), ci]
+            getattr(L, pfx + "estimate_sigma").restype = C.c_double
+            getattr(L, pfx + "estimate_sigma").argtypes = [vp]
+            getattr(L, pfx + "threshold_bands").argtypes = [vp, vp, ci]
+            getattr(L, pfx + "denoise").restype = C.c_double
+            getattr(L, pfx + "denoise").argtypes = [vp, ci, C.c_double, ci, vp]
         _host[dt] = L
     return _host[dt]
 

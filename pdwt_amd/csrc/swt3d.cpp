@@ -7,6 +7,7 @@
 
 #include "../../include/pdwt_hip.h"
 #include "../../include/swt3d.h"
+#include "bandstats_host.hpp"
 
 
 #ifndef DOUBLEPRECISION
@@ -266,6 +267,89 @@ void StationaryWavelets3D::set_coeff(DTYPE* coeff, int num, int mem_is_on_device
 intptr_t StationaryWavelets3D::image_int_ptr(void) { return (intptr_t)d_image; }
 intptr_t StationaryWavelets3D::coeff_int_ptr(int num) { return (d_coeffs && band_shape(num, NULL, NULL, NULL) > 0) ? (intptr_t)d_coeffs[num] : 0; }
 
+// ---- band statistics and noise-adaptive thresholds (include/swt3d.h; the shared host half: bandstats_host.hpp) ----
+// pointer and size of every band; nb = 0 unless the coefficients are valid
+static pdwt_bl::BandList band_list(const StationaryWavelets3D& W)
+{
+    pdwt_bl::BandList bl;
+    bl.nb = 0;
+    if (!(W.state == W_FORWARD || W.state == W_THRESHOLD) || !W.d_coeffs) return bl;
+    const int nb = W.num_bands();
+    if (nb < 2 || nb > pdwt_bl::kMaxBands) return bl;
+    for (int k = 0; k < nb; k++) {
+        const long long n = W.band_shape(k, NULL, NULL, NULL);
+        if (n <= 0 || !W.d_coeffs[k]) return bl;
+        bl.ptr[k] = W.d_coeffs[k];
+        bl.n[k] = (size_t)n;
+    }
+    bl.nb = nb;
+    bl.finest = 7 * W.winfos.nlevels;  // ddd of level 1
+    bl.samples = (double)W.winfos.Nz * W.winfos.Nr * W.winfos.Nc;
+    return bl;
+}
+
+int StationaryWavelets3D::band_stats(int num, w_band_stats* out, int with_median)
+{
+    ON_MY_DEVICE3();
+    const pdwt_bl::BandList bl = band_list(*this);
+    if (!bl.nb || num < 0 || num >= bl.nb || !out) return PDWT_EINVAL;
+    const int rc = pdwt_bl::stats(bl, num, out, with_median);
+    if (rc != PDWT_OK) report3("StationaryWavelets3D::band_stats()", rc);
+    return rc;
+}
+
+int StationaryWavelets3D::all_band_stats(w_band_stats* out, int with_median)
+{
+    ON_MY_DEVICE3();
+    const pdwt_bl::BandList bl = band_list(*this);
+    if (!bl.nb || !out) return PDWT_EINVAL;
+    const int rc = pdwt_bl::stats(bl, -1, out, with_median);
+    if (rc != PDWT_OK) report3("StationaryWavelets3D::all_band_stats()", rc);
+    return rc;
+}
+
+double StationaryWavelets3D::estimate_sigma()
+{
+    ON_MY_DEVICE3();
+    const pdwt_bl::BandList bl = band_list(*this);
+    double sigma = -1.0;
+    if (!bl.nb) return -1.0;
+    const int rc = pdwt_bl::estimate_sigma(bl, &sigma);
+    if (rc != PDWT_OK) {
+        report3("StationaryWavelets3D::estimate_sigma()", rc);
+        return -1.0;
+    }
+    return sigma;
+}
+
+void StationaryWavelets3D::threshold_bands(const DTYPE* betas, int kind)
+{
+    ON_MY_DEVICE3();
+    const pdwt_bl::BandList bl = band_list(*this);
+    if (!bl.nb || !betas || (kind != 0 && kind != 1)) return;
+    const int rc = pdwt_bl::threshold(bl, betas, kind);
+    if (rc != PDWT_OK) {
+        report3("StationaryWavelets3D::threshold_bands()", rc);
+        state = W_THRESHOLD_ERROR;
+    }
+}
+
+double StationaryWavelets3D::denoise(int method, double sigma, int kind, DTYPE* betas_out)
+{
+    ON_MY_DEVICE3();
+    const pdwt_bl::BandList bl = band_list(*this);
+    if (!bl.nb || (method != 0 && method != 1) || (kind != 0 && kind != 1)) return -1.0;
+    DTYPE betas[pdwt_bl::kMaxBands];
+    const int rc = pdwt_bl::denoise(bl, method, kind, &sigma, betas);
+    if (rc != PDWT_OK) {
+        report3("StationaryWavelets3D::denoise()", rc);
+        state = W_THRESHOLD_ERROR;
+        return -1.0;
+    }
+    if (betas_out) memcpy(betas_out, betas, (size_t)bl.nb * sizeof(DTYPE));
+    return sigma;
+}
+
 // ---- flat C handle API (pdwt_amd/swt3d.py) -------------------------------------------------------
 #define SW3(h) (static_cast<StationaryWavelets3D*>(h))
 extern "C" {
@@ -290,4 +374,9 @@ int pdwt_swt3d_state(void* h) { return (int)SW3(h)->state; }
 void pdwt_swt3d_info(void* h, w_info3d* out) { *out = SW3(h)->winfos; }
 intptr_t pdwt_swt3d_image_int_ptr(void* h) { return SW3(h)->image_int_ptr(); }
 intptr_t pdwt_swt3d_coeff_int_ptr(void* h, int num) { return SW3(h)->coeff_int_ptr(num); }
+int pdwt_swt3d_band_stats(void* h, int num, w_band_stats* out, int with_median) { return SW3(h)->band_stats(num, out, with_median); }
+int pdwt_swt3d_all_band_stats(void* h, w_band_stats* out, int with_median) { return SW3(h)->all_band_stats(out, with_median); }
+double pdwt_swt3d_estimate_sigma(void* h) { return SW3(h)->estimate_sigma(); }
+void pdwt_swt3d_threshold_bands(void* h, const DTYPE* betas, int kind) { SW3(h)->threshold_bands(betas, kind); }
+double pdwt_swt3d_denoise(void* h, int method, double sigma, int kind, DTYPE* betas_out) { return SW3(h)->denoise(method, sigma, kind, betas_out); }
 }

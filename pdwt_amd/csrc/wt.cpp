@@ -16,6 +16,7 @@
 
 #include "../../include/pdwt_hip.h"
 #include "../../include/wt.h"
+#include "bandstats_host.hpp"
 
 static_assert(sizeof(w_info) == sizeof(pdwt_info), "w_info must mirror pdwt_info");
 
@@ -587,6 +588,92 @@ void Wavelets::proj_linf(DTYPE beta, int do_thresh_appcoeffs)
 {
     ON_MY_DEVICE();
     PDWT_THRESH_METHOD("proj_linf", SFX(pdwt_proj_linf)(d_coeffs, beta, to_pdwt(winfos), do_thresh_appcoeffs))
+}
+
+// ---- band statistics and noise-adaptive thresholds (ADDITIONS, include/wt.h; the shared host half: bandstats_host.hpp) ----
+// pointer and logical size (pdwt_band_size: band 0 is allocated at the level-1 size) of every band; nb = 0 unless the coefficients are valid
+static pdwt_bl::BandList band_list(const Wavelets& W)
+{
+    pdwt_bl::BandList bl;
+    bl.nb = 0;
+    if (!(W.state == W_FORWARD || W.state == W_THRESHOLD) || !W.d_coeffs) return bl;
+    const pdwt_info w = to_pdwt(W.winfos);
+    const int nb = pdwt_num_bands(w);
+    if (nb < 2 || nb > pdwt_bl::kMaxBands) return bl;
+    for (int k = 0; k < nb; k++) {
+        const long long n = pdwt_band_size(w, k, NULL, NULL);
+        if (n <= 0 || !W.d_coeffs[k]) return bl;
+        bl.ptr[k] = W.d_coeffs[k];
+        bl.n[k] = (size_t)n;
+    }
+    bl.nb = nb;
+    bl.finest = (W.winfos.ndims == 2) ? 3 : 1;
+    bl.samples = (W.winfos.ndims == 2) ? (double)W.winfos.Nr * W.winfos.Nc : (double)W.winfos.Nc;
+    return bl;
+}
+
+int Wavelets::band_stats(int num, w_band_stats* out, int with_median)
+{
+    ON_MY_DEVICE();
+    const pdwt_bl::BandList bl = band_list(*this);
+    if (!bl.nb || num < 0 || num >= bl.nb || !out) return PDWT_EINVAL;
+    const int rc = pdwt_bl::stats(bl, num, out, with_median);
+    if (rc != PDWT_OK) report("Wavelets::band_stats()", rc);
+    return rc;
+}
+
+int Wavelets::all_band_stats(w_band_stats* out, int with_median)
+{
+    ON_MY_DEVICE();
+    const pdwt_bl::BandList bl = band_list(*this);
+    if (!bl.nb || !out) return PDWT_EINVAL;
+    const int rc = pdwt_bl::stats(bl, -1, out, with_median);
+    if (rc != PDWT_OK) report("Wavelets::all_band_stats()", rc);
+    return rc;
+}
+
+double Wavelets::estimate_sigma()
+{
+    ON_MY_DEVICE();
+    const pdwt_bl::BandList bl = band_list(*this);
+    double sigma = -1.0;
+    if (!bl.nb) return -1.0;
+    const int rc = pdwt_bl::estimate_sigma(bl, &sigma);
+    if (rc != PDWT_OK) {
+        report("Wavelets::estimate_sigma()", rc);
+        return -1.0;
+    }
+    return sigma;
+}
+
+void Wavelets::threshold_bands(const DTYPE* betas, int kind)
+{
+    ON_MY_DEVICE();
+    const pdwt_bl::BandList bl = band_list(*this);
+    if (!bl.nb || !betas || (kind != 0 && kind != 1)) return;
+    coeffs_changed(filters_);  // a cached sum |c| (set_norm_cache) would be stale: dropped as set_coeff drops it
+    const int rc = pdwt_bl::threshold(bl, betas, kind);
+    if (rc != PDWT_OK) {
+        report("Wavelets::threshold_bands()", rc);
+        state = W_THRESHOLD_ERROR;
+    }
+}
+
+double Wavelets::denoise(int method, double sigma, int kind, DTYPE* betas_out)
+{
+    ON_MY_DEVICE();
+    const pdwt_bl::BandList bl = band_list(*this);
+    if (!bl.nb || (method != 0 && method != 1) || (kind != 0 && kind != 1)) return -1.0;
+    DTYPE betas[pdwt_bl::kMaxBands];
+    coeffs_changed(filters_);
+    const int rc = pdwt_bl::denoise(bl, method, kind, &sigma, betas);
+    if (rc != PDWT_OK) {
+        report("Wavelets::denoise()", rc);
+        state = W_THRESHOLD_ERROR;
+        return -1.0;
+    }
+    if (betas_out) memcpy(betas_out, betas, (size_t)bl.nb * sizeof(DTYPE));
+    return sigma;
 }
 
 // src/wt.cu:364-366: if inplace = 1 the result is in d_image, otherwise in d_tmp

@@ -63,6 +63,12 @@ intptr_t pdwt_wavelets_coeffs_table_ptr(void* h)
     return (intptr_t)W(h)->d_coeffs;
 }
 intptr_t pdwt_wavelets_tmp_int_ptr(void* h) { return (intptr_t)W(h)->d_tmp; }
+/* band statistics and noise-adaptive thresholds (include/wt.h) */
+int pdwt_wavelets_band_stats(void* h, int num, w_band_stats* out, int with_median) { return W(h)->band_stats(num, out, with_median); }
+int pdwt_wavelets_all_band_stats(void* h, w_band_stats* out, int with_median) { return W(h)->all_band_stats(out, with_median); }
+double pdwt_wavelets_estimate_sigma(void* h) { return W(h)->estimate_sigma(); }
+void pdwt_wavelets_threshold_bands(void* h, const DTYPE* betas, int kind) { W(h)->threshold_bands(betas, kind); }
+double pdwt_wavelets_denoise(void* h, int method, double sigma, int kind, DTYPE* betas_out) { return W(h)->denoise(method, sigma, kind, betas_out); }
 
 /* batch of equally sized 2-D images, every level of all images in one launch (include/wt_batch.h: WaveletsImages) */
 void* pdwt_images_new(DTYPE* imgs, int B, int Nr, int Nc, const char* wname, int levels, int memisonhost)

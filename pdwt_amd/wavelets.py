@@ -64,7 +64,74 @@ def _device_source(img):
     return None
 
 
-class Wavelets:
+class _BandStatsAPI:
+    """band_stats / all_band_stats / estimate_sigma / threshold_bands / denoise (include/wt.h ADDITIONS; kernels: bandstats.hip), shared by
+    ``Wavelets``, ``Wavelets3D`` and ``StationaryWavelets3D``: ``_hpfx`` names the handle API.  All five need valid coefficients
+    (after ``forward()``, before ``inverse()``): ``RuntimeError`` otherwise.  Everything is computed on the device; the statistics
+    synchronise (one small copy to the host)."""
+
+    _hpfx = "pdwt_wavelets_"
+    METHODS = {"visu": 0, "bayes": 1}
+    KINDS = {"soft": 0, "hard": 1}
+
+    def _bs(self, name):
+        return getattr(self._L, self._hpfx + name)
+
+    def band_stats(self, num, with_median=True):
+        """{n, sum_abs, sum_sq, max_abs, median_abs} of band ``num``: the sums accumulated in double, max and median exact
+        (``median_abs`` = mean of the two middle order statistics of |c|; NaN unless ``with_median``)."""
+        if not 0 <= int(num) < self.nbands:
+            raise IndexError(num)
+        s = N.BandStats()
+        if self._bs("band_stats")(self._h, int(num), C.byref(s), int(bool(with_median))) != 0:
+            raise RuntimeError("band_stats(%d) refused (state=%d): the coefficients are not valid" % (num, self.state))
+        return s.as_dict()
+
+    def all_band_stats(self, with_median=False):
+        """band_stats of every band, as a list, from ONE moments launch over all bands."""
+        out = (N.BandStats * max(self.nbands, 1))()
+        if self._bs("all_band_stats")(self._h, out, int(bool(with_median))) != 0:
+            raise RuntimeError("all_band_stats refused (state=%d): the coefficients are not valid" % self.state)
+        return [out[k].as_dict() for k in range(self.nbands)]
+
+    def estimate_sigma(self):
+        """Noise level from the finest diagonal band: median |D1| / 0.6744897501960817 (``ddd`` of level 1 in 3-D; one value for
+        all rows of a batched 1-D instance)."""
+        s = float(self._bs("estimate_sigma")(self._h))
+        if s < 0:
+            raise RuntimeError("estimate_sigma refused (state=%d): the coefficients are not valid" % self.state)
+        return s
+
+    def threshold_bands(self, betas, kind="soft"):
+        """One beta per band (``nbands`` values); a negative beta leaves its band alone.  ``kind``: "soft" or "hard"."""
+        if kind not in self.KINDS:
+            raise ValueError("kind must be 'soft' or 'hard'")
+        b = np.ascontiguousarray(betas, dtype=self.dtype).ravel()
+        if b.size != self.nbands:
+            raise ValueError("%d betas for %d bands" % (b.size, self.nbands))
+        if self.state not in (W_FORWARD, W_THRESHOLD):
+            raise RuntimeError("threshold_bands refused (state=%d): the coefficients are not valid" % self.state)
+        self._bs("threshold_bands")(self._h, b.ctypes.data_as(C.c_void_p), self.KINDS[kind])
+
+    def denoise(self, method="bayes", sigma=None, kind="soft"):
+        """VisuShrink (``"visu"``: sigma * sqrt(2 ln N) on every detail band) or BayesShrink (``"bayes"``: sigma^2 / sqrt(ms_b - sigma^2)
+        per detail band, the band zeroed when ms_b <= sigma^2), applied in place; ``sigma=None`` estimates it.  The rules assume an
+        orthonormal bank.  Returns {"sigma": the sigma used, "betas": ndarray(nbands), betas[0] == -1: band 0 is never touched}."""
+        if method not in self.METHODS:
+            raise ValueError("method must be 'visu' or 'bayes'")
+        if kind not in self.KINDS:
+            raise ValueError("kind must be 'soft' or 'hard'")
+        if sigma is not None and not float(sigma) >= 0:
+            raise ValueError("sigma must be >= 0 (None: estimated)")
+        betas = np.zeros(max(self.nbands, 1), dtype=self.dtype)
+        s = float(self._bs("denoise")(self._h, self.METHODS[method], -1.0 if sigma is None else float(sigma), self.KINDS[kind],
+                                      betas.ctypes.data_as(C.c_void_p)))
+        if s < 0:
+            raise RuntimeError("denoise refused (state=%d): the coefficients are not valid" % self.state)
+        return {"sigma": s, "betas": betas[:self.nbands]}
+
+
+class Wavelets(_BandStatsAPI):
     def __init__(self, img, wname, levels, do_separable=1, do_cycle_spinning=0, do_swt=0, ndim=2, dtype=None, shape=None, device_ptr=None,
                  norm_cache=True):
         """Wavelets(img, Nr, Nc, wname, levels, memisonhost, do_separable, do_cycle_spinning, do_swt, ndim)

@@ -8,16 +8,18 @@ import ctypes as C
 import numpy as np
 
 from . import _native as N
-from .wavelets import DeviceArray, _device_source, _sync_producer
+from .wavelets import DeviceArray, _BandStatsAPI, _device_source, _sync_producer
 
 # detail bands of one level, in storage order (band 1 + 7*(L - lev) + k is BAND_KEYS[k] of level lev, 1 = finest)
 BAND_KEYS = ("aad", "ada", "add", "daa", "dad", "dda", "ddd")
 
 
-class Wavelets3D:
+class Wavelets3D(_BandStatsAPI):
     """Wavelets3D(vol, wname, levels): ``vol`` is a 3-D numpy array (Nz, Nr, Nc) or a contiguous float32 / float64 torch
     tensor on the GPU (copied device to device into the instance, as Wavelets does: no host round trip).  Same state machine as ``Wavelets``.
     Not in 3-D: SWT, non-separable and custom banks, cycle spinning, group_soft_threshold, shrink, proj_linf (ValueError)."""
+
+    _hpfx = "pdwt_wavelets3d_"  # (StationaryWavelets3D maps the prefix onto its own handle API)
 
     def __init__(self, vol, wname, levels, dtype=None, do_swt=0, do_separable=1, do_cycle_spinning=0):
         if do_swt or not do_separable or do_cycle_spinning:
