@@ -334,7 +334,8 @@ PDWT_DECL_NONSEP(double, f64)
  * Sizes: any Nz <= 65535 and Nr * Nc < 2^31 (a plane is indexed in 32 bits; the volume itself may exceed 2^31 elements);
  * anything else is PDWT_EINVAL / a NULL buffer / a scratch size of 0.
  * d_tmp: pdwt_tmp_elems3d(info) elements, about 1.13x the volume (the four x-y quadrants of level 1 + one level-1 approximation).
- * Kernels: pdwt_amd/csrc/dwt3d.hip, two launches per level and direction (an x-y tile kernel and a z kernel).
+ * Kernels: pdwt_amd/csrc/dwt3d.hip, two launches per level and direction (an x-y tile kernel and a z kernel); the band table and
+ * its walks (thresholds, norm1): pdwt_amd/csrc/vol3d.hpp, shared with the stationary transform.
  * The thresholds and norm1 follow the 2-D semantics (pdwt_soft_thresh_* / pdwt_hard_thresh_* / pdwt_norm1_*) with 7 detail
  * bands per level: normalize > 0 divides beta by sqrt(2) per level, the approximation takes beta / sqrt(2)^L (soft) or the
  * un-normalised beta (hard), norm1 sums |c| over all bands, band 0 included, in double.
@@ -375,7 +376,7 @@ int pdwt_norm1_3d_f64(double** d_coeffs, pdwt_info3d info, double* out);
  * Geometry: Nz <= 65535, Nr * Nc < 2^31, an even hlen of the bank table, and 1 <= nlevels <= ilog2(min(Nz, Nr, Nc) / (hlen - 1))
  * (so (hlen - 1) * 2^(L-1) < min(Nz, Nr, Nc)); anything else is PDWT_EINVAL / a NULL buffer / a scratch size of 0.
  * d_tmp: pdwt_tmp_elems_swt3d(info) elements, 4 volumes (the four x-y quadrants of a level).
- * Kernels: pdwt_amd/csrc/swt3d.hip, two launches per level and direction (an x-y tile kernel and a z kernel).
+ * Kernels: pdwt_amd/csrc/swt3d.hip, two launches per level and direction (an x-y tile kernel and a z kernel); band table: vol3d.hpp.
  * The thresholds and norm1 follow the 3-D DWT rules above with full-size bands.
  * ------------------------------------------------------------------------------------------- */
 int pdwt_num_bands_swt3d(pdwt_info3d info);                                                    /* 7L+1, or PDWT_EINVAL */

@@ -1,5 +1,5 @@
 /*
- * wt3d.h -- `Wavelets3D`: the separable, decimated, periodised 3-D DWT of a volume (no reference counterpart: the
+ * wt3d.h -- `Wavelets3D` (and `Transform3D`, the base it shares with `StationaryWavelets3D` of swt3d.h): the separable, decimated, periodised 3-D DWT of a volume (no reference counterpart: the
  * reference's Wavelets refuses ndims == 3).  Same build as wt.h: plain host C++, DTYPE = float (libpdwt.so) or double
  * (-DDOUBLEPRECISION, libpdwtd.so), every device action a C-ABI call into libpdwt_hip.so (include/pdwt_hip.h).
  *
@@ -26,7 +26,11 @@ struct w_info3d {
     int hlen;    /* filter length */
 };
 
-class Wavelets3D {
+struct w_ops3d; /* what one transform contributes: its name, entry points and the two texts that differ (pdwt_amd/csrc/wt3d.cpp) */
+
+/* Everything `Wavelets3D` and `StationaryWavelets3D` (swt3d.h) share, which is all but their constructors: one implementation in
+ * pdwt_amd/csrc/wt3d.cpp, the transform chosen by the table the derived constructor passes in.  Not instantiable, not copyable. */
+class Transform3D {
   public:
     DTYPE* d_image;   /* device: volume / reconstruction */
     DTYPE** d_coeffs; /* host array of 7L+1 device pointers (one allocation) */
@@ -34,9 +38,6 @@ class Wavelets3D {
     char wname[128];
     w_info3d winfos;
     w_state state;
-
-    Wavelets3D(DTYPE* vol, int Nz, int Nr, int Nc, const char* wname, int levels, int memisonhost = 1);
-    ~Wavelets3D();
 
     void forward();
     void inverse();
@@ -71,10 +72,20 @@ class Wavelets3D {
     void threshold_bands(const DTYPE* betas, int kind = 0);
     double denoise(int method, double sigma = -1.0, int kind = 0, DTYPE* betas_out = NULL);
 
+  protected:
+    Transform3D(const w_ops3d& ops, DTYPE* vol, int Nz, int Nr, int Nc, const char* wname, int levels, int memisonhost);
+    ~Transform3D(); /* not virtual: destroy an instance through its concrete class */
+
   private:
-    void* filters_; /* per-instance bank + device */
-    Wavelets3D(const Wavelets3D&);
-    Wavelets3D& operator=(const Wavelets3D&);
+    const w_ops3d* ops_; /* set first: valid after every W_CREATION_ERROR return */
+    void* filters_;      /* per-instance bank + device */
+    Transform3D(const Transform3D&);
+    Transform3D& operator=(const Transform3D&);
+};
+
+class Wavelets3D : public Transform3D {
+  public:
+    Wavelets3D(DTYPE* vol, int Nz, int Nr, int Nc, const char* wname, int levels, int memisonhost = 1);
 };
 
 #endif

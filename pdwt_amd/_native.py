@@ -250,7 +250,7 @@ def host(dtype):
             getattr(L, "pdwt_images_" + n).argtypes = [vp]
         L.pdwt_wavelets_coeff_int_ptr.restype = C.c_ssize_t
         L.pdwt_wavelets_coeff_int_ptr.argtypes = [vp, ci]
-        # Wavelets3D (include/wt3d.h, wt3d.cpp) and StationaryWavelets3D (include/swt3d.h, swt3d.cpp): the same handle API
+        # Wavelets3D (include/wt3d.h) and StationaryWavelets3D (include/swt3d.h), both in wt3d.cpp: the same handle API
         for pfx in ("pdwt_wavelets3d_", "pdwt_swt3d_"):
             getattr(L, pfx + "new").restype = vp
             getattr(L, pfx + "new").argtypes = [vp, ci, ci, ci, C.c_char_p, ci, ci]

@@ -9,8 +9,7 @@
 // composing the 1-D level along the axes (Haar excepted, within 1 ulp: the oracle's 1-D Haar level scales a +- b in double).
 // Traffic per level: one read of the input (plus the tile halos) and one write of the quadrants, then one read of the quadrants
 // and one write of the bands -- twice the compulsory bytes of a fully fused level.
-#include "common.hpp"
-#include "bandlist.hpp"
+#include "vol3d.hpp"
 
 namespace pdwt {
 
@@ -40,15 +39,6 @@ template <typename T, int HL>
 constexpr size_t inv_xy_lds()
 {
     return sizeof(T) * (4 * (size_t)(ITY / 2 + HL / 2) * (ITX / 2 + HL / 2) + 2 * (size_t)ITY * (ITX / 2 + HL / 2));
-}
-
-// 0 that the compiler cannot see through: a tap index offset by it is not loop-invariant, so the scalar loads of the taps are
-// issued inside each loop instead of all hoisted in front of the loops (2*HL doubles of a long bank do not fit the SGPRs)
-__device__ __forceinline__ int opaque_zero()
-{
-    int z = 0;
-    asm volatile("" : "+s"(z));
-    return z;
 }
 
 template <typename T, int HL>
@@ -266,30 +256,20 @@ static int launch_level(int dir, int pass, const XYJob<T>& xy, const ZJob<T>& zj
     return PDWT_OK;
 }
 
-// every even length of the bank table (2 .. 40)
-template <typename T, int HL = 2>
+template <typename T>
 static int run_pass(int hlen, int dir, int pass, const XYJob<T>& xy, const ZJob<T>& zj, int nz, const Taps2<T>& taps)
 {
-    if constexpr (HL > PDWT_MAX_FILTER_WIDTH) {
-        return PDWT_EINVAL;
-    } else {
-        if (hlen == HL) return launch_level<T, HL>(dir, pass, xy, zj, nz, taps);
-        return run_pass<T, HL + 2>(hlen, dir, pass, xy, zj, nz, taps);
-    }
+    return with_filter_length(hlen, [&](auto hl) { return launch_level<T, decltype(hl)::value>(dir, pass, xy, zj, nz, taps); });
 }
 
 // ---- geometry ------------------------------------------------------------------------------------
-constexpr int k3MaxLevels = 13;  // 7*13 + 1 = 92 bands <= the 97 of the band-table kernels (utils.hip)
-
 struct Geom3 {
     int L;
-    int z[k3MaxLevels + 1], y[k3MaxLevels + 1], x[k3MaxLevels + 1];  // level-l volume, l = 0 .. L
+    int z[kVolMaxLevels + 1], y[kVolMaxLevels + 1], x[kVolMaxLevels + 1];  // level-l volume, l = 0 .. L
 };
 static bool geom3(const pdwt_info3d& w, Geom3* g)
 {
-    if (w.Nz < 1 || w.Nr < 1 || w.Nc < 1 || w.nlevels < 1 || w.nlevels > k3MaxLevels) return false;
-    // a plane is indexed with 32 bits (lanes across it) and z is a grid dimension: Nr * Nc < 2^31, Nz <= 65535
-    if ((unsigned long long)w.Nr * (unsigned long long)w.Nc >= (1ull << 31) || w.Nz > 65535) return false;
+    if (!vol_sizes_ok(w)) return false;
     g->L = w.nlevels;
     g->z[0] = w.Nz;
     g->y[0] = w.Nr;
@@ -301,7 +281,6 @@ static bool geom3(const pdwt_info3d& w, Geom3* g)
     }
     return true;
 }
-static size_t pad64(size_t n) { return (n + 63) & ~(size_t)63; }  // 256-byte multiples for either precision
 
 // d_tmp = [Q: the 4 quadrants (z, hy, hx) | A: hz*hy*hx] at level-1 geometry (the largest of every level)
 struct Tmp3 {
@@ -316,13 +295,6 @@ static Tmp3 tmp3(const Geom3& g)
     t.total = t.abuf + pad64(hz * hy * hx);
     return t;
 }
-
-// band index of detail k (0..6: aad, ada, add, daa, dad, dda, ddd) of level lev (1 = finest)
-static inline int band3(int L, int lev, int k) { return 1 + 7 * (L - lev) + k; }
-
-// the z pass pairs: quadrant q (2 * x band + y band) -> (z low, z high) detail index of the level (-1: the approximation)
-//   q0 (y a, x a): aaa, daa    q1 (y d, x a): ada, dda    q2 (y a, x d): aad, dad    q3 (y d, x d): add, ddd
-static const int kZLow[4] = {-1, 1, 0, 2}, kZHigh[4] = {3, 5, 4, 6};
 
 template <typename T>
 static int forward3d(T* img, T** c, T* tmp, pdwt_info3d w, const typename FiltersOf<T>::type* f)
@@ -396,80 +368,27 @@ static long long band_size3(const pdwt_info3d& w, int num, int* bz, int* by, int
     return (long long)g.z[lev] * g.y[lev] * g.x[lev];
 }
 
+// the band walks of vol3d.hpp over this geometry
 template <typename T>
 static T** create3(pdwt_info3d w)
 {
     Geom3 g;
     if (!geom3(w, &g)) return nullptr;
-    const int nb = 7 * g.L + 1;
-    size_t off[7 * k3MaxLevels + 1];
-    size_t total = 0;
-    for (int k = 0; k < nb; k++) {
-        off[k] = total;
-        total += ((size_t)band_size3(w, k, nullptr, nullptr, nullptr) * sizeof(T) + 255) & ~(size_t)255;
-    }
-    char* base = (char*)pdwt_malloc(total);
-    if (!base) return nullptr;
-    if (pdwt_memset(base, 0, total) != PDWT_OK) {
-        (void)pdwt_free(base);
-        return nullptr;
-    }
-    T** tab = (T**)calloc((size_t)nb + 1, sizeof(T*));  // slot [-1]: the allocation base (as coeffs.hip)
-    if (!tab) {
-        (void)pdwt_free(base);
-        return nullptr;
-    }
-    tab[0] = (T*)base;
-    for (int k = 0; k < nb; k++) tab[k + 1] = (T*)(base + off[k]);
-    return tab + 1;
+    return vol_create_bands<T>(g.L, [&](int k) { return band_size3(w, k, nullptr, nullptr, nullptr); });
 }
-template <typename T>
-static int destroy3(T** c)
-{
-    if (!c) return PDWT_OK;
-    const int rc = pdwt_free((void*)c[-1]);
-    free(c - 1);
-    return rc;
-}
-
-// thresholds: the 2-D rules of utils.hip ew_bands with 7 detail bands per level
 template <typename T>
 static int thresh3(int op, T** c, T beta, pdwt_info3d w, int do_thresh_appcoeffs, int normalize)
 {
     Geom3 g;
     if (!c || !geom3(w, &g)) return PDWT_EINVAL;
-    T* ptr[7 * k3MaxLevels + 1];
-    size_t n[7 * k3MaxLevels + 1];
-    T b[7 * k3MaxLevels + 1];
-    int nb = 0;
-    if (do_thresh_appcoeffs) {
-        T beta2 = beta;
-        if (normalize > 0 && op == BL_SOFT) {  // beta / sqrt(2)^nlevels, as in 2-D (src/common.cu:231-235)
-            const int nl2 = g.L / 2;
-            beta2 /= (T)(1 << nl2);
-            if (nl2 * 2 != g.L) beta2 = (T)(beta2 / 1.4142135623730951);
-        }
-        ptr[nb] = c[0], n[nb] = (size_t)band_size3(w, 0, nullptr, nullptr, nullptr), b[nb] = beta2, nb++;
-    }
-    for (int lev = 1; lev <= g.L; lev++) {
-        if (normalize > 0) beta = (T)(beta / 1.4142135623730951);
-        for (int k = 0; k < 7; k++) {
-            const int num = band3(g.L, lev, k);
-            ptr[nb] = c[num], n[nb] = (size_t)band_size3(w, num, nullptr, nullptr, nullptr), b[nb] = beta, nb++;
-        }
-    }
-    return band_list_ew<T>(op, ptr, n, b, nb);
+    return vol_thresh<T>(op, c, beta, g.L, do_thresh_appcoeffs, normalize, [&](int k) { return band_size3(w, k, nullptr, nullptr, nullptr); });
 }
 template <typename T>
 static int norm1_3(T** c, pdwt_info3d w, double* out)
 {
     Geom3 g;
     if (!c || !out || !geom3(w, &g)) return PDWT_EINVAL;
-    T* ptr[7 * k3MaxLevels + 1];
-    size_t n[7 * k3MaxLevels + 1];
-    const int nb = 7 * g.L + 1;
-    for (int k = 0; k < nb; k++) ptr[k] = c[k], n[k] = (size_t)band_size3(w, k, nullptr, nullptr, nullptr);
-    return band_list_abs_sum<T>(ptr, n, nb, out);
+    return vol_norm1<T>(c, g.L, out, [&](int k) { return band_size3(w, k, nullptr, nullptr, nullptr); });
 }
 
 }  // namespace pdwt
@@ -490,8 +409,8 @@ size_t pdwt_tmp_elems3d(pdwt_info3d w)
 }
 float** pdwt_create_coeffs_buffer3d_f32(pdwt_info3d w) { return create3<float>(w); }
 double** pdwt_create_coeffs_buffer3d_f64(pdwt_info3d w) { return create3<double>(w); }
-int pdwt_free_coeffs_buffer3d_f32(float** c, pdwt_info3d) { return destroy3(c); }
-int pdwt_free_coeffs_buffer3d_f64(double** c, pdwt_info3d) { return destroy3(c); }
+int pdwt_free_coeffs_buffer3d_f32(float** c, pdwt_info3d) { return vol_free_bands(c); }
+int pdwt_free_coeffs_buffer3d_f64(double** c, pdwt_info3d) { return vol_free_bands(c); }
 int pdwt_forward3d_separable_f32(float* img, float** c, float* tmp, pdwt_info3d w, const pdwt_filters_f32* f) { return forward3d<float>(img, c, tmp, w, f); }
 int pdwt_forward3d_separable_f64(double* img, double** c, double* tmp, pdwt_info3d w, const pdwt_filters_f64* f) { return forward3d<double>(img, c, tmp, w, f); }
 int pdwt_inverse3d_separable_f32(float* img, float** c, float* tmp, pdwt_info3d w, const pdwt_filters_f32* f) { return inverse3d<float>(img, c, tmp, w, f); }

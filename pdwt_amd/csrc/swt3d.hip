@@ -12,8 +12,7 @@
 // Per output the tap order and the one FMA per tap are the oracle's analysis; the synthesis uses pre-halved taps in one FMA
 // (the 2-D SWT kernels' deviation).
 // Traffic per level: forward 1 read + 4 writes (x-y) + 4 reads + 8 writes (z) = 17 volumes against 9 compulsory; inverse mirrored.
-#include "common.hpp"
-#include "bandlist.hpp"
+#include "vol3d.hpp"
 
 namespace pdwt {
 
@@ -40,14 +39,6 @@ constexpr size_t swt_inv_xy_lds()
     return sizeof(T) * (2 * (size_t)(STY + HL - 1) * (STX + HL - 1) + 2 * (size_t)STY * (STX + HL - 1));
 }
 
-// 0 that the compiler cannot see through (dwt3d.hip): keeps the scalar tap loads inside each loop for the long banks
-__device__ __forceinline__ int swt_opaque_zero()
-{
-    int z = 0;
-    asm volatile("" : "+s"(z));
-    return z;
-}
-
 // sa += sum_j pa[j * stride] * ta[HL-1-j], sd += sum_j pd[j * stride] * tb[HL-1-j] (one FMA per tap, j ascending).  The taps are
 // re-read per chunk of 8 behind a fresh opaque zero: hoisted all at once, the 2*40 taps of the inverse overflowed the SGPRs.
 template <typename T, int HL>
@@ -55,7 +46,7 @@ __device__ __forceinline__ void fma_taps2(const T* pa, const T* pd, int stride, 
 {
 #pragma unroll
     for (int j0 = 0; j0 < HL; j0 += 8) {
-        const int z0 = swt_opaque_zero();
+        const int z0 = opaque_zero();
 #pragma unroll
         for (int j = j0; j < (j0 + 8 < HL ? j0 + 8 : HL); j++) {
             sa = fma_t<T>(pa[j * stride], taps.a[HL - 1 - j + z0], sa);
@@ -93,7 +84,7 @@ __global__ __launch_bounds__(kSXYThreads) void k_swt_fwd_xy(SXYJob<T> job, Taps2
     for (int e = tid; e < RI * STX; e += kSXYThreads) {
         const int r = e / STX, ox = e % STX;
         const T* p = in + r * CI + ox;
-        const int z0 = swt_opaque_zero();
+        const int z0 = opaque_zero();
         T sl = T(0), sh = T(0);
 #pragma unroll
         for (int j = 0; j < HL; j++) {
@@ -113,7 +104,7 @@ __global__ __launch_bounds__(kSXYThreads) void k_swt_fwd_xy(SXYJob<T> job, Taps2
 #pragma unroll
         for (int xb = 0; xb < 2; xb++) {
             const T* p = rb + xb * RI * STX + oy * STX + ox;
-            const int z0 = swt_opaque_zero();
+            const int z0 = opaque_zero();
             T sl = T(0), sh = T(0);
 #pragma unroll
             for (int j = 0; j < HL; j++) {
@@ -277,49 +268,34 @@ static int swt_launch(int dir, int pass, const SXYJob<T>& xy, const SZJob<T>& zj
     return PDWT_OK;
 }
 
-// every even length of the bank table (2 .. 40)
-template <typename T, int HL = 2>
+template <typename T>
 static int swt_run_pass(int hlen, int dir, int pass, const SXYJob<T>& xy, const SZJob<T>& zj, int nz, const Taps2<T>& taps)
 {
-    if constexpr (HL > PDWT_MAX_FILTER_WIDTH) {
-        return PDWT_EINVAL;
-    } else {
-        if (hlen == HL) return swt_launch<T, HL>(dir, pass, xy, zj, nz, taps);
-        return swt_run_pass<T, HL + 2>(hlen, dir, pass, xy, zj, nz, taps);
-    }
+    return with_filter_length(hlen, [&](auto hl) { return swt_launch<T, decltype(hl)::value>(dir, pass, xy, zj, nz, taps); });
 }
 
 // ---- geometry ------------------------------------------------------------------------------------
-constexpr int kS3MaxLevels = 13;  // 7*13 + 1 = 92 bands <= the 97 of the band-table kernels (utils.hip)
-
 // Nz <= 65535 (a grid dimension), Nr * Nc < 2^31 (a plane is indexed in 32 bits), an even hlen of the table, and the level clamp
 // (hlen - 1) * 2^(L-1) < min(Nz, Nr, Nc): one periodic wrap reaches every tap, and every sublattice index r + f*(m - c + j) of
 // the kernels stays far inside 32 bits (min(N)^2 <= Nr * Nc < 2^31).
 static bool swt_geom(const pdwt_info3d& w)
 {
-    if (w.Nz < 1 || w.Nr < 1 || w.Nc < 1 || w.nlevels < 1 || w.nlevels > kS3MaxLevels) return false;
-    if ((unsigned long long)w.Nr * (unsigned long long)w.Nc >= (1ull << 31) || w.Nz > 65535) return false;
+    if (!vol_sizes_ok(w)) return false;
     if (w.hlen < 2 || w.hlen > PDWT_MAX_FILTER_WIDTH || (w.hlen & 1)) return false;
     int n = w.Nz < w.Nr ? w.Nz : w.Nr;
     if (w.Nc < n) n = w.Nc;
     return (long long)(w.hlen - 1) << (w.nlevels - 1) < n;
 }
 static size_t swt_vol(const pdwt_info3d& w) { return (size_t)w.Nz * w.Nr * w.Nc; }
-static size_t swt_pad64(size_t n) { return (n + 63) & ~(size_t)63; }  // 256-byte multiples for either precision
 // d_tmp = the 4 full-size x-y quadrants of a level
-static size_t swt_tmp_elems(const pdwt_info3d& w) { return 4 * swt_pad64(swt_vol(w)); }
-
-// band index of detail k (0..6: aad, ada, add, daa, dad, dda, ddd) of level lev (1 = finest), as dwt3d.hip
-static inline int swt_band(int L, int lev, int k) { return 1 + 7 * (L - lev) + k; }
-// quadrant q (2 * x band + y band) -> (z low, z high) detail index (-1: the approximation), as dwt3d.hip
-static const int kSZLow[4] = {-1, 1, 0, 2}, kSZHigh[4] = {3, 5, 4, 6};
+static size_t swt_tmp_elems(const pdwt_info3d& w) { return 4 * pad64(swt_vol(w)); }
 
 template <typename T>
 static int swt_forward3d(T* img, T** c, T* tmp, pdwt_info3d w, const typename FiltersOf<T>::type* f)
 {
     if (!img || !c || !tmp || !f || !swt_geom(w) || f->hlen != w.hlen) return PDWT_EINVAL;
     const Taps2<T> taps = taps_fwd<T>(f);
-    const size_t sq = swt_pad64(swt_vol(w));
+    const size_t sq = pad64(swt_vol(w));
     for (int lev = 1; lev <= w.nlevels; lev++) {
         SXYJob<T> xy{};
         xy.src = (lev == 1) ? img : c[0];  // the approximation of the level above passes through band 0
@@ -329,8 +305,8 @@ static int swt_forward3d(T* img, T** c, T* tmp, pdwt_info3d w, const typename Fi
         SZJob<T> zj{};
         for (int q = 0; q < 4; q++) {
             zj.src[q] = tmp + q * sq;
-            zj.lo[q] = (q == 0) ? c[0] : c[swt_band(w.nlevels, lev, kSZLow[q])];
-            zj.hi[q] = c[swt_band(w.nlevels, lev, kSZHigh[q])];
+            zj.lo[q] = (q == 0) ? c[0] : c[band3(w.nlevels, lev, kZLow[q])];
+            zj.hi[q] = c[band3(w.nlevels, lev, kZHigh[q])];
         }
         zj.n = w.Nz, zj.plane = w.Nr * w.Nc, zj.f = xy.f;
         // x-y into the quadrants (reads band 0), then z into the bands (overwrites band 0: already read)
@@ -346,12 +322,12 @@ static int swt_inverse3d(T* img, T** c, T* tmp, pdwt_info3d w, const typename Fi
 {
     if (!img || !c || !tmp || !f || !swt_geom(w) || f->hlen != w.hlen) return PDWT_EINVAL;
     const Taps2<T> taps = taps_inv<T>(f, T(0.5));  // pre-halved: one FMA per tap
-    const size_t sq = swt_pad64(swt_vol(w));
+    const size_t sq = pad64(swt_vol(w));
     for (int lev = w.nlevels; lev >= 1; lev--) {
         SZJob<T> zj{};
         for (int q = 0; q < 4; q++) {
-            zj.src[q] = (q == 0) ? ((lev == w.nlevels) ? c[0] : img) : c[swt_band(w.nlevels, lev, kSZLow[q])];
-            zj.src2[q] = c[swt_band(w.nlevels, lev, kSZHigh[q])];
+            zj.src[q] = (q == 0) ? ((lev == w.nlevels) ? c[0] : img) : c[band3(w.nlevels, lev, kZLow[q])];
+            zj.src2[q] = c[band3(w.nlevels, lev, kZHigh[q])];
             zj.lo[q] = tmp + q * sq;
         }
         zj.n = w.Nz, zj.plane = w.Nr * w.Nc, zj.f = 1 << (lev - 1);
@@ -367,71 +343,24 @@ static int swt_inverse3d(T* img, T** c, T* tmp, pdwt_info3d w, const typename Fi
     return PDWT_OK;
 }
 
-// ---- band table: 7L+1 full-size bands in one zero-filled allocation at 256-byte offsets -----------------------------
+// ---- band table: 7L+1 full-size bands, through the band walks of vol3d.hpp ------------------------------------------
 template <typename T>
 static T** swt_create(pdwt_info3d w)
 {
     if (!swt_geom(w)) return nullptr;
-    const int nb = 7 * w.nlevels + 1;
-    const size_t step = (swt_vol(w) * sizeof(T) + 255) & ~(size_t)255, total = step * nb;
-    char* base = (char*)pdwt_malloc(total);
-    if (!base) return nullptr;
-    if (pdwt_memset(base, 0, total) != PDWT_OK) {
-        (void)pdwt_free(base);
-        return nullptr;
-    }
-    T** tab = (T**)calloc((size_t)nb + 1, sizeof(T*));  // slot [-1]: the allocation base (as coeffs.hip)
-    if (!tab) {
-        (void)pdwt_free(base);
-        return nullptr;
-    }
-    tab[0] = (T*)base;
-    for (int k = 0; k < nb; k++) tab[k + 1] = (T*)(base + step * k);
-    return tab + 1;
+    return vol_create_bands<T>(w.nlevels, [&](int) { return swt_vol(w); });
 }
-template <typename T>
-static int swt_destroy(T** c)
-{
-    if (!c) return PDWT_OK;
-    const int rc = pdwt_free((void*)c[-1]);
-    free(c - 1);
-    return rc;
-}
-
-// thresholds: the rules of dwt3d.hip thresh3 (the reference's do_swt branch of w_call_soft_thresh / w_call_hard_thresh)
 template <typename T>
 static int swt_thresh(int op, T** c, T beta, pdwt_info3d w, int do_thresh_appcoeffs, int normalize)
 {
     if (!c || !swt_geom(w)) return PDWT_EINVAL;
-    const int L = w.nlevels;
-    T* ptr[7 * kS3MaxLevels + 1];
-    size_t n[7 * kS3MaxLevels + 1];
-    T b[7 * kS3MaxLevels + 1];
-    int nb = 0;
-    if (do_thresh_appcoeffs) {
-        T beta2 = beta;
-        if (normalize > 0 && op == BL_SOFT) {  // beta / sqrt(2)^nlevels (src/common.cu:231-235)
-            const int nl2 = L / 2;
-            beta2 /= (T)(1 << nl2);
-            if (nl2 * 2 != L) beta2 = (T)(beta2 / 1.4142135623730951);
-        }
-        ptr[nb] = c[0], n[nb] = swt_vol(w), b[nb] = beta2, nb++;  // hard: the un-normalised beta (SURVEY B-4)
-    }
-    for (int lev = 1; lev <= L; lev++) {
-        if (normalize > 0) beta = (T)(beta / 1.4142135623730951);
-        for (int k = 0; k < 7; k++) ptr[nb] = c[swt_band(L, lev, k)], n[nb] = swt_vol(w), b[nb] = beta, nb++;
-    }
-    return band_list_ew<T>(op, ptr, n, b, nb);
+    return vol_thresh<T>(op, c, beta, w.nlevels, do_thresh_appcoeffs, normalize, [&](int) { return swt_vol(w); });
 }
 template <typename T>
 static int swt_norm1(T** c, pdwt_info3d w, double* out)
 {
     if (!c || !out || !swt_geom(w)) return PDWT_EINVAL;
-    T* ptr[7 * kS3MaxLevels + 1];
-    size_t n[7 * kS3MaxLevels + 1];
-    const int nb = 7 * w.nlevels + 1;
-    for (int k = 0; k < nb; k++) ptr[k] = c[k], n[k] = swt_vol(w);
-    return band_list_abs_sum<T>(ptr, n, nb, out);
+    return vol_norm1<T>(c, w.nlevels, out, [&](int) { return swt_vol(w); });
 }
 
 }  // namespace pdwt
@@ -451,8 +380,8 @@ long long pdwt_band_size_swt3d(pdwt_info3d w, int num, int* bz, int* by, int* bx
 size_t pdwt_tmp_elems_swt3d(pdwt_info3d w) { return swt_geom(w) ? swt_tmp_elems(w) : 0; }
 float** pdwt_create_coeffs_buffer_swt3d_f32(pdwt_info3d w) { return swt_create<float>(w); }
 double** pdwt_create_coeffs_buffer_swt3d_f64(pdwt_info3d w) { return swt_create<double>(w); }
-int pdwt_free_coeffs_buffer_swt3d_f32(float** c, pdwt_info3d) { return swt_destroy(c); }
-int pdwt_free_coeffs_buffer_swt3d_f64(double** c, pdwt_info3d) { return swt_destroy(c); }
+int pdwt_free_coeffs_buffer_swt3d_f32(float** c, pdwt_info3d) { return vol_free_bands(c); }
+int pdwt_free_coeffs_buffer_swt3d_f64(double** c, pdwt_info3d) { return vol_free_bands(c); }
 int pdwt_forward3d_swt_f32(float* img, float** c, float* tmp, pdwt_info3d w, const pdwt_filters_f32* f) { return swt_forward3d<float>(img, c, tmp, w, f); }
 int pdwt_forward3d_swt_f64(double* img, double** c, double* tmp, pdwt_info3d w, const pdwt_filters_f64* f) { return swt_forward3d<double>(img, c, tmp, w, f); }
 int pdwt_inverse3d_swt_f32(float* img, float** c, float* tmp, pdwt_info3d w, const pdwt_filters_f32* f) { return swt_inverse3d<float>(img, c, tmp, w, f); }

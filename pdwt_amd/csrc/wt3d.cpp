@@ -1,12 +1,14 @@
-// wt3d.cpp -- host side of `Wavelets3D` (include/wt3d.h) above the 3-D entry points of include/pdwt_hip.h, and its flat C
-// handle API (pdwt_wavelets3d_*, the shape of wt_capi.cpp).  Plain host C++ like wt.cpp, built into libpdwt.so (float) and
-// libpdwtd.so (-DDOUBLEPRECISION).  The state machine is the one of Wavelets (wt.cpp, reference src/wt.cu).
+// wt3d.cpp -- host side of the two volume classes, `Wavelets3D` (include/wt3d.h) and `StationaryWavelets3D` (include/swt3d.h), above
+// the 3-D entry points of include/pdwt_hip.h, and their flat C handle APIs (pdwt_wavelets3d_*, pdwt_swt3d_*, the shape of
+// wt_capi.cpp).  Every method is written once, on their base `Transform3D`; what differs between the transforms is one `w_ops3d` table
+// each.  Plain host C++ like wt.cpp, built into libpdwt.so (float) and libpdwtd.so (-DDOUBLEPRECISION).  The state machine is the one
+// of Wavelets (wt.cpp, reference src/wt.cu).
 #include <limits.h>
 #include <new>
 #include <string.h>
 
 #include "../../include/pdwt_hip.h"
-#include "../../include/wt3d.h"
+#include "../../include/swt3d.h"
 #include "bandstats_host.hpp"
 
 static_assert(sizeof(w_info3d) == sizeof(pdwt_info3d), "w_info3d must mirror pdwt_info3d");
@@ -18,6 +20,33 @@ typedef pdwt_filters_f32 filters3_t;
 #define SFX(name) name##_f64
 typedef pdwt_filters_f64 filters3_t;
 #endif
+
+// What one transform contributes to the shared class: its name in messages, its entry points of include/pdwt_hip.h in this build's
+// precision, and the two texts that differ.  The only place that knows which transform an instance runs.
+struct w_ops3d {
+    const char* name;
+    size_t (*tmp_elems)(pdwt_info3d);
+    DTYPE** (*create_coeffs_buffer)(pdwt_info3d);
+    int (*free_coeffs_buffer)(DTYPE**, pdwt_info3d);
+    int (*forward)(DTYPE*, DTYPE**, DTYPE*, pdwt_info3d, const filters3_t*);
+    int (*inverse)(DTYPE*, DTYPE**, DTYPE*, pdwt_info3d, const filters3_t*);
+    int (*soft_thresh)(DTYPE**, DTYPE, pdwt_info3d, int, int);
+    int (*hard_thresh)(DTYPE**, DTYPE, pdwt_info3d, int, int);
+    int (*norm1)(DTYPE**, pdwt_info3d, double*);
+    int (*num_bands)(pdwt_info3d);
+    long long (*band_size)(pdwt_info3d, int, int*, int*, int*);
+    const char* thresh_after_inverse;     // after the name: the threshold refused in state W_INVERSE
+    const char* get_coeff_after_inverse;  // get_coeff() refused in state W_INVERSE
+};
+static const w_ops3d kDwtOps = {
+    "Wavelets3D", pdwt_tmp_elems3d, SFX(pdwt_create_coeffs_buffer3d), SFX(pdwt_free_coeffs_buffer3d), SFX(pdwt_forward3d_separable),
+    SFX(pdwt_inverse3d_separable), SFX(pdwt_soft_thresh3d), SFX(pdwt_hard_thresh3d), SFX(pdwt_norm1_3d), pdwt_num_bands3d, pdwt_band_size3d,
+    "cannot threshold coefficients, as they were modified by W.inverse()",
+    "inverse() has been performed, the coefficients has been modified and do not make sense anymore."};
+static const w_ops3d kSwtOps = {
+    "StationaryWavelets3D", pdwt_tmp_elems_swt3d, SFX(pdwt_create_coeffs_buffer_swt3d), SFX(pdwt_free_coeffs_buffer_swt3d), SFX(pdwt_forward3d_swt),
+    SFX(pdwt_inverse3d_swt), SFX(pdwt_soft_thresh_swt3d), SFX(pdwt_hard_thresh_swt3d), SFX(pdwt_norm1_swt3d), pdwt_num_bands_swt3d, pdwt_band_size_swt3d,
+    "cannot threshold coefficients after W.inverse() (run forward() first)", "inverse() has been performed; run forward() first."};
 
 namespace {
 struct state3_t {
@@ -44,12 +73,13 @@ struct DevScope3 {
         if (mine >= 0 && prev >= 0 && prev != mine) pdwt_set_device(prev);
     }
 };
-void report3(const char* where, int rc) { printf("ERROR: %s failed (code %d): %s\n", where, rc, pdwt_last_error_string()); }
+// "ERROR: <class><where> failed ...": where = "::method()" or "(): what"
+void report3(const w_ops3d* ops, const char* where, int rc) { printf("ERROR: %s%s failed (code %d): %s\n", ops->name, where, rc, pdwt_last_error_string()); }
 }  // namespace
 #define ON_MY_DEVICE3() DevScope3 dev_scope_(filters_)
 
-Wavelets3D::Wavelets3D(DTYPE* vol, int Nz, int Nr, int Nc, const char* wname_, int levels, int memisonhost)
-    : d_image(NULL), d_coeffs(NULL), d_tmp(NULL), state(W_INIT), filters_(NULL)
+Transform3D::Transform3D(const w_ops3d& ops, DTYPE* vol, int Nz, int Nr, int Nc, const char* wname_, int levels, int memisonhost)
+    : d_image(NULL), d_coeffs(NULL), d_tmp(NULL), state(W_INIT), ops_(&ops), filters_(NULL)
 {
     winfos.Nz = Nz;
     winfos.Nr = Nr;
@@ -59,7 +89,7 @@ Wavelets3D::Wavelets3D(DTYPE* vol, int Nz, int Nr, int Nc, const char* wname_, i
     strncpy(wname, wname_ ? wname_ : "", 127);
     wname[127] = 0;
     if (Nz < 1 || Nr < 1 || Nc < 1 || !wname_) {
-        puts("ERROR: Wavelets3D(): invalid volume size or wavelet name");
+        printf("ERROR: %s(): invalid volume size or wavelet name\n", ops_->name);
         state = W_CREATION_ERROR;
         return;
     }
@@ -96,17 +126,17 @@ Wavelets3D::Wavelets3D(DTYPE* vol, int Nz, int Nr, int Nc, const char* wname_, i
         return;
     }
     const pdwt_info3d w = to_pdwt3(winfos);
-    const size_t n = (size_t)Nz * Nr * Nc, ntmp = pdwt_tmp_elems3d(w);
+    const size_t n = (size_t)Nz * Nr * Nc, ntmp = ops_->tmp_elems(w);
     if (ntmp == 0) {
-        puts("ERROR: Wavelets3D(): unsupported volume size (Nz <= 65535 and Nr * Nc < 2^31 are required)");
+        printf("ERROR: %s(): unsupported volume size (Nz <= 65535 and Nr * Nc < 2^31 are required)\n", ops_->name);
         state = W_CREATION_ERROR;
         return;
     }
     d_image = (DTYPE*)pdwt_malloc(n * sizeof(DTYPE));
     d_tmp = (DTYPE*)pdwt_malloc(ntmp * sizeof(DTYPE));
-    d_coeffs = SFX(pdwt_create_coeffs_buffer3d)(w);
+    d_coeffs = ops_->create_coeffs_buffer(w);
     if (!d_image || !d_tmp || !d_coeffs) {
-        printf("ERROR: Wavelets3D(): device allocation failed: %s\n", pdwt_last_error_string());
+        printf("ERROR: %s(): device allocation failed: %s\n", ops_->name, pdwt_last_error_string());
         state = W_CREATION_ERROR;
         return;
     }
@@ -115,37 +145,37 @@ Wavelets3D::Wavelets3D(DTYPE* vol, int Nz, int Nr, int Nc, const char* wname_, i
     else if (memisonhost) rc = pdwt_memcpy_h2d(d_image, vol, n * sizeof(DTYPE));
     else rc = pdwt_memcpy_d2d_foreign(d_image, vol, n * sizeof(DTYPE));
     if (rc != PDWT_OK) {
-        report3("Wavelets3D(): volume upload", rc);
+        report3(ops_, "(): volume upload", rc);
         state = W_CREATION_ERROR;
     }
 }
 
-Wavelets3D::~Wavelets3D()
+Transform3D::~Transform3D()
 {
     ON_MY_DEVICE3();
     if (d_image) pdwt_free(d_image);
-    if (d_coeffs) SFX(pdwt_free_coeffs_buffer3d)(d_coeffs, to_pdwt3(winfos));
+    if (d_coeffs) ops_->free_coeffs_buffer(d_coeffs, to_pdwt3(winfos));
     if (d_tmp) pdwt_free(d_tmp);
     free(filters_);
 }
 
-void Wavelets3D::forward()
+void Transform3D::forward()
 {
     ON_MY_DEVICE3();
     if (state == W_CREATION_ERROR) {
         puts("Warning: forward transform not computed, as there was an error when creating the wavelets");
         return;
     }
-    const int rc = SFX(pdwt_forward3d_separable)(d_image, d_coeffs, d_tmp, to_pdwt3(winfos), &S(filters_)->f);
+    const int rc = ops_->forward(d_image, d_coeffs, d_tmp, to_pdwt3(winfos), &S(filters_)->f);
     if (rc != PDWT_OK) {
-        report3("Wavelets3D::forward()", rc);
+        report3(ops_, "::forward()", rc);
         state = W_FORWARD_ERROR;
         return;
     }
     state = W_FORWARD;
 }
 
-void Wavelets3D::inverse()
+void Transform3D::inverse()
 {
     ON_MY_DEVICE3();
     if (state == W_INVERSE) {
@@ -156,57 +186,57 @@ void Wavelets3D::inverse()
         puts("Warning: inverse transform not computed, as there was an error in a previous stage");
         return;
     }
-    const int rc = SFX(pdwt_inverse3d_separable)(d_image, d_coeffs, d_tmp, to_pdwt3(winfos), &S(filters_)->f);
+    const int rc = ops_->inverse(d_image, d_coeffs, d_tmp, to_pdwt3(winfos), &S(filters_)->f);
     if (rc != PDWT_OK) {
-        report3("Wavelets3D::inverse()", rc);
+        report3(ops_, "::inverse()", rc);
         state = W_INVERSE_ERROR;
         return;
     }
     state = W_INVERSE;
 }
 
-void Wavelets3D::soft_threshold(DTYPE beta, int do_thresh_appcoeffs, int normalize)
+void Transform3D::soft_threshold(DTYPE beta, int do_thresh_appcoeffs, int normalize)
 {
     ON_MY_DEVICE3();
     if (state == W_INVERSE) {
-        puts("Warning: Wavelets3D(): cannot threshold coefficients, as they were modified by W.inverse()");
+        printf("Warning: %s(): %s\n", ops_->name, ops_->thresh_after_inverse);
         return;
     }
     if (state == W_CREATION_ERROR) return;
-    const int rc = SFX(pdwt_soft_thresh3d)(d_coeffs, beta, to_pdwt3(winfos), do_thresh_appcoeffs, normalize);
+    const int rc = ops_->soft_thresh(d_coeffs, beta, to_pdwt3(winfos), do_thresh_appcoeffs, normalize);
     if (rc != PDWT_OK) {
-        report3("Wavelets3D::soft_threshold()", rc);
+        report3(ops_, "::soft_threshold()", rc);
         state = W_THRESHOLD_ERROR;
     }
 }
 
-void Wavelets3D::hard_threshold(DTYPE beta, int do_thresh_appcoeffs, int normalize)
+void Transform3D::hard_threshold(DTYPE beta, int do_thresh_appcoeffs, int normalize)
 {
     ON_MY_DEVICE3();
     if (state == W_INVERSE) {
-        puts("Warning: Wavelets3D(): cannot threshold coefficients, as they were modified by W.inverse()");
+        printf("Warning: %s(): %s\n", ops_->name, ops_->thresh_after_inverse);
         return;
     }
     if (state == W_CREATION_ERROR) return;
-    const int rc = SFX(pdwt_hard_thresh3d)(d_coeffs, beta, to_pdwt3(winfos), do_thresh_appcoeffs, normalize);
+    const int rc = ops_->hard_thresh(d_coeffs, beta, to_pdwt3(winfos), do_thresh_appcoeffs, normalize);
     if (rc != PDWT_OK) {
-        report3("Wavelets3D::hard_threshold()", rc);
+        report3(ops_, "::hard_threshold()", rc);
         state = W_THRESHOLD_ERROR;
     }
 }
 
-double Wavelets3D::norm1_double()
+double Transform3D::norm1_double()
 {
     ON_MY_DEVICE3();
     if (state == W_CREATION_ERROR) return 0;
     double d = 0;
-    const int rc = SFX(pdwt_norm1_3d)(d_coeffs, to_pdwt3(winfos), &d);
-    if (rc != PDWT_OK) report3("Wavelets3D::norm1()", rc);
+    const int rc = ops_->norm1(d_coeffs, to_pdwt3(winfos), &d);
+    if (rc != PDWT_OK) report3(ops_, "::norm1()", rc);
     return d;
 }
-DTYPE Wavelets3D::norm1() { return (DTYPE)norm1_double(); }
+DTYPE Transform3D::norm1() { return (DTYPE)norm1_double(); }
 
-int Wavelets3D::get_image(DTYPE* res)
+int Transform3D::get_image(DTYPE* res)
 {
     ON_MY_DEVICE3();
     if (!d_image || !res) return 0;
@@ -215,30 +245,30 @@ int Wavelets3D::get_image(DTYPE* res)
     return n > (size_t)INT_MAX ? INT_MAX : (int)n;
 }
 
-void Wavelets3D::set_image(DTYPE* vol, int mem_is_on_device)
+void Transform3D::set_image(DTYPE* vol, int mem_is_on_device)
 {
     ON_MY_DEVICE3();
     if (!d_image || !vol) return;
     const size_t nb = (size_t)winfos.Nz * winfos.Nr * winfos.Nc * sizeof(DTYPE);
     const int rc = mem_is_on_device ? pdwt_memcpy_d2d_foreign(d_image, vol, nb) : pdwt_memcpy_h2d(d_image, vol, nb);
-    if (rc != PDWT_OK) report3("Wavelets3D::set_image()", rc);
+    if (rc != PDWT_OK) report3(ops_, "::set_image()", rc);
     if (state != W_CREATION_ERROR) state = W_INIT;
 }
 
-int Wavelets3D::num_bands() const { return state == W_CREATION_ERROR ? 0 : pdwt_num_bands3d(to_pdwt3(winfos)); }
+int Transform3D::num_bands() const { return state == W_CREATION_ERROR ? 0 : ops_->num_bands(to_pdwt3(winfos)); }
 
-long long Wavelets3D::band_shape(int num, int* bz, int* by, int* bx) const
+long long Transform3D::band_shape(int num, int* bz, int* by, int* bx) const
 {
     if (state == W_CREATION_ERROR) return 0;
-    const long long n = pdwt_band_size3d(to_pdwt3(winfos), num, bz, by, bx);
+    const long long n = ops_->band_size(to_pdwt3(winfos), num, bz, by, bx);
     return n > 0 ? n : 0;
 }
 
-int Wavelets3D::get_coeff(DTYPE* coeff, int num)
+int Transform3D::get_coeff(DTYPE* coeff, int num)
 {
     ON_MY_DEVICE3();
     if (state == W_INVERSE) {
-        puts("Warning: get_coeff(): inverse() has been performed, the coefficients has been modified and do not make sense anymore.");
+        printf("Warning: get_coeff(): %s\n", ops_->get_coeff_after_inverse);
         return 0;
     }
     if (!d_coeffs || !coeff) return 0;
@@ -251,7 +281,7 @@ int Wavelets3D::get_coeff(DTYPE* coeff, int num)
     return n > (long long)INT_MAX ? INT_MAX : (int)n;
 }
 
-void Wavelets3D::set_coeff(DTYPE* coeff, int num, int mem_is_on_device)
+void Transform3D::set_coeff(DTYPE* coeff, int num, int mem_is_on_device)
 {
     ON_MY_DEVICE3();
     if (!d_coeffs || !coeff) return;
@@ -262,15 +292,15 @@ void Wavelets3D::set_coeff(DTYPE* coeff, int num, int mem_is_on_device)
     }
     const size_t nb = (size_t)n * sizeof(DTYPE);
     const int rc = mem_is_on_device ? pdwt_memcpy_d2d_foreign(d_coeffs[num], coeff, nb) : pdwt_memcpy_h2d(d_coeffs[num], coeff, nb);
-    if (rc != PDWT_OK) report3("Wavelets3D::set_coeff()", rc);
+    if (rc != PDWT_OK) report3(ops_, "::set_coeff()", rc);
 }
 
-intptr_t Wavelets3D::image_int_ptr(void) { return (intptr_t)d_image; }
-intptr_t Wavelets3D::coeff_int_ptr(int num) { return (d_coeffs && band_shape(num, NULL, NULL, NULL) > 0) ? (intptr_t)d_coeffs[num] : 0; }
+intptr_t Transform3D::image_int_ptr(void) { return (intptr_t)d_image; }
+intptr_t Transform3D::coeff_int_ptr(int num) { return (d_coeffs && band_shape(num, NULL, NULL, NULL) > 0) ? (intptr_t)d_coeffs[num] : 0; }
 
-// ---- band statistics and noise-adaptive thresholds (include/wt3d.h; the shared host half: bandstats_host.hpp) ----
+// ---- band statistics and noise-adaptive thresholds (include/wt3d.h; the host half shared with Wavelets: bandstats_host.hpp) ----
 // pointer and size of every band; nb = 0 unless the coefficients are valid
-static pdwt_bl::BandList band_list(const Wavelets3D& W)
+static pdwt_bl::BandList band_list(const Transform3D& W)
 {
     pdwt_bl::BandList bl;
     bl.nb = 0;
@@ -289,27 +319,27 @@ static pdwt_bl::BandList band_list(const Wavelets3D& W)
     return bl;
 }
 
-int Wavelets3D::band_stats(int num, w_band_stats* out, int with_median)
+int Transform3D::band_stats(int num, w_band_stats* out, int with_median)
 {
     ON_MY_DEVICE3();
     const pdwt_bl::BandList bl = band_list(*this);
     if (!bl.nb || num < 0 || num >= bl.nb || !out) return PDWT_EINVAL;
     const int rc = pdwt_bl::stats(bl, num, out, with_median);
-    if (rc != PDWT_OK) report3("Wavelets3D::band_stats()", rc);
+    if (rc != PDWT_OK) report3(ops_, "::band_stats()", rc);
     return rc;
 }
 
-int Wavelets3D::all_band_stats(w_band_stats* out, int with_median)
+int Transform3D::all_band_stats(w_band_stats* out, int with_median)
 {
     ON_MY_DEVICE3();
     const pdwt_bl::BandList bl = band_list(*this);
     if (!bl.nb || !out) return PDWT_EINVAL;
     const int rc = pdwt_bl::stats(bl, -1, out, with_median);
-    if (rc != PDWT_OK) report3("Wavelets3D::all_band_stats()", rc);
+    if (rc != PDWT_OK) report3(ops_, "::all_band_stats()", rc);
     return rc;
 }
 
-double Wavelets3D::estimate_sigma()
+double Transform3D::estimate_sigma()
 {
     ON_MY_DEVICE3();
     const pdwt_bl::BandList bl = band_list(*this);
@@ -317,25 +347,25 @@ double Wavelets3D::estimate_sigma()
     if (!bl.nb) return -1.0;
     const int rc = pdwt_bl::estimate_sigma(bl, &sigma);
     if (rc != PDWT_OK) {
-        report3("Wavelets3D::estimate_sigma()", rc);
+        report3(ops_, "::estimate_sigma()", rc);
         return -1.0;
     }
     return sigma;
 }
 
-void Wavelets3D::threshold_bands(const DTYPE* betas, int kind)
+void Transform3D::threshold_bands(const DTYPE* betas, int kind)
 {
     ON_MY_DEVICE3();
     const pdwt_bl::BandList bl = band_list(*this);
     if (!bl.nb || !betas || (kind != 0 && kind != 1)) return;
     const int rc = pdwt_bl::threshold(bl, betas, kind);
     if (rc != PDWT_OK) {
-        report3("Wavelets3D::threshold_bands()", rc);
+        report3(ops_, "::threshold_bands()", rc);
         state = W_THRESHOLD_ERROR;
     }
 }
 
-double Wavelets3D::denoise(int method, double sigma, int kind, DTYPE* betas_out)
+double Transform3D::denoise(int method, double sigma, int kind, DTYPE* betas_out)
 {
     ON_MY_DEVICE3();
     const pdwt_bl::BandList bl = band_list(*this);
@@ -343,7 +373,7 @@ double Wavelets3D::denoise(int method, double sigma, int kind, DTYPE* betas_out)
     DTYPE betas[pdwt_bl::kMaxBands];
     const int rc = pdwt_bl::denoise(bl, method, kind, &sigma, betas);
     if (rc != PDWT_OK) {
-        report3("Wavelets3D::denoise()", rc);
+        report3(ops_, "::denoise()", rc);
         state = W_THRESHOLD_ERROR;
         return -1.0;
     }
@@ -351,33 +381,44 @@ double Wavelets3D::denoise(int method, double sigma, int kind, DTYPE* betas_out)
     return sigma;
 }
 
-// ---- flat C handle API (pdwt_amd/wavelets3d.py) -------------------------------------------------------
-#define W3(h) (static_cast<Wavelets3D*>(h))
-extern "C" {
-void* pdwt_wavelets3d_new(DTYPE* vol, int Nz, int Nr, int Nc, const char* wname, int levels, int memisonhost)
+// ---- the two classes: a constructor each, which names the table ----------------------------------------
+Wavelets3D::Wavelets3D(DTYPE* vol, int Nz, int Nr, int Nc, const char* wname_, int levels, int memisonhost)
+    : Transform3D(kDwtOps, vol, Nz, Nr, Nc, wname_, levels, memisonhost)
 {
-    return new (std::nothrow) Wavelets3D(vol, Nz, Nr, Nc, wname, levels, memisonhost);
 }
-void pdwt_wavelets3d_delete(void* h) { delete W3(h); }
-void pdwt_wavelets3d_forward(void* h) { W3(h)->forward(); }
-void pdwt_wavelets3d_inverse(void* h) { W3(h)->inverse(); }
-void pdwt_wavelets3d_soft_threshold(void* h, DTYPE beta, int app, int normalize) { W3(h)->soft_threshold(beta, app, normalize); }
-void pdwt_wavelets3d_hard_threshold(void* h, DTYPE beta, int app, int normalize) { W3(h)->hard_threshold(beta, app, normalize); }
-DTYPE pdwt_wavelets3d_norm1(void* h) { return W3(h)->norm1(); }
-double pdwt_wavelets3d_norm1_f64(void* h) { return W3(h)->norm1_double(); }
-int pdwt_wavelets3d_get_image(void* h, DTYPE* out) { return W3(h)->get_image(out); }
-void pdwt_wavelets3d_set_image(void* h, DTYPE* vol, int mem_is_on_device) { W3(h)->set_image(vol, mem_is_on_device); }
-int pdwt_wavelets3d_num_bands(void* h) { return W3(h)->num_bands(); }
-long long pdwt_wavelets3d_band_shape(void* h, int num, int* bz, int* by, int* bx) { return W3(h)->band_shape(num, bz, by, bx); }
-int pdwt_wavelets3d_get_coeff(void* h, DTYPE* out, int num) { return W3(h)->get_coeff(out, num); }
-void pdwt_wavelets3d_set_coeff(void* h, DTYPE* in, int num, int mem_is_on_device) { W3(h)->set_coeff(in, num, mem_is_on_device); }
-int pdwt_wavelets3d_state(void* h) { return (int)W3(h)->state; }
-void pdwt_wavelets3d_info(void* h, w_info3d* out) { *out = W3(h)->winfos; }
-intptr_t pdwt_wavelets3d_image_int_ptr(void* h) { return W3(h)->image_int_ptr(); }
-intptr_t pdwt_wavelets3d_coeff_int_ptr(void* h, int num) { return W3(h)->coeff_int_ptr(num); }
-int pdwt_wavelets3d_band_stats(void* h, int num, w_band_stats* out, int with_median) { return W3(h)->band_stats(num, out, with_median); }
-int pdwt_wavelets3d_all_band_stats(void* h, w_band_stats* out, int with_median) { return W3(h)->all_band_stats(out, with_median); }
-double pdwt_wavelets3d_estimate_sigma(void* h) { return W3(h)->estimate_sigma(); }
-void pdwt_wavelets3d_threshold_bands(void* h, const DTYPE* betas, int kind) { W3(h)->threshold_bands(betas, kind); }
-double pdwt_wavelets3d_denoise(void* h, int method, double sigma, int kind, DTYPE* betas_out) { return W3(h)->denoise(method, sigma, kind, betas_out); }
+StationaryWavelets3D::StationaryWavelets3D(DTYPE* vol, int Nz, int Nr, int Nc, const char* wname_, int levels, int memisonhost)
+    : Transform3D(kSwtOps, vol, Nz, Nr, Nc, wname_, levels, memisonhost)
+{
 }
+
+// ---- flat C handle APIs (pdwt_amd/wavelets3d.py, pdwt_amd/swt3d.py): one list, stamped out per class -------------------
+// new and delete go through the concrete class (the destructor of Transform3D is not virtual)
+#define PDWT_HANDLE_API3(P, CLS) \
+    void* P##new(DTYPE* vol, int Nz, int Nr, int Nc, const char* wname, int levels, int memisonhost) { return new (std::nothrow) CLS(vol, Nz, Nr, Nc, wname, levels, memisonhost); } \
+    void P##delete(void* h) { delete static_cast<CLS*>(h); } \
+    void P##forward(void* h) { static_cast<CLS*>(h)->forward(); } \
+    void P##inverse(void* h) { static_cast<CLS*>(h)->inverse(); } \
+    void P##soft_threshold(void* h, DTYPE beta, int app, int normalize) { static_cast<CLS*>(h)->soft_threshold(beta, app, normalize); } \
+    void P##hard_threshold(void* h, DTYPE beta, int app, int normalize) { static_cast<CLS*>(h)->hard_threshold(beta, app, normalize); } \
+    DTYPE P##norm1(void* h) { return static_cast<CLS*>(h)->norm1(); } \
+    double P##norm1_f64(void* h) { return static_cast<CLS*>(h)->norm1_double(); } \
+    int P##get_image(void* h, DTYPE* out) { return static_cast<CLS*>(h)->get_image(out); } \
+    void P##set_image(void* h, DTYPE* vol, int mem_is_on_device) { static_cast<CLS*>(h)->set_image(vol, mem_is_on_device); } \
+    int P##num_bands(void* h) { return static_cast<CLS*>(h)->num_bands(); } \
+    long long P##band_shape(void* h, int num, int* bz, int* by, int* bx) { return static_cast<CLS*>(h)->band_shape(num, bz, by, bx); } \
+    int P##get_coeff(void* h, DTYPE* out, int num) { return static_cast<CLS*>(h)->get_coeff(out, num); } \
+    void P##set_coeff(void* h, DTYPE* in, int num, int mem_is_on_device) { static_cast<CLS*>(h)->set_coeff(in, num, mem_is_on_device); } \
+    int P##state(void* h) { return (int)static_cast<CLS*>(h)->state; } \
+    void P##info(void* h, w_info3d* out) { *out = static_cast<CLS*>(h)->winfos; } \
+    intptr_t P##image_int_ptr(void* h) { return static_cast<CLS*>(h)->image_int_ptr(); } \
+    intptr_t P##coeff_int_ptr(void* h, int num) { return static_cast<CLS*>(h)->coeff_int_ptr(num); } \
+    int P##band_stats(void* h, int num, w_band_stats* out, int with_median) { return static_cast<CLS*>(h)->band_stats(num, out, with_median); } \
+    int P##all_band_stats(void* h, w_band_stats* out, int with_median) { return static_cast<CLS*>(h)->all_band_stats(out, with_median); } \
+    double P##estimate_sigma(void* h) { return static_cast<CLS*>(h)->estimate_sigma(); } \
+    void P##threshold_bands(void* h, const DTYPE* betas, int kind) { static_cast<CLS*>(h)->threshold_bands(betas, kind); } \
+    double P##denoise(void* h, int method, double sigma, int kind, DTYPE* betas_out) { return static_cast<CLS*>(h)->denoise(method, sigma, kind, betas_out); }
+extern "C" {
+PDWT_HANDLE_API3(pdwt_wavelets3d_, Wavelets3D)
+PDWT_HANDLE_API3(pdwt_swt3d_, StationaryWavelets3D)
+}
+#undef PDWT_HANDLE_API3

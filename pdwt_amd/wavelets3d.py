@@ -19,12 +19,17 @@ class Wavelets3D(_BandStatsAPI):
     tensor on the GPU (copied device to device into the instance, as Wavelets does: no host round trip).  Same state machine as ``Wavelets``.
     Not in 3-D: SWT, non-separable and custom banks, cycle spinning, group_soft_threshold, shrink, proj_linf (ValueError)."""
 
-    _hpfx = "pdwt_wavelets3d_"  # (StationaryWavelets3D maps the prefix onto its own handle API)
+    _hpfx = "pdwt_wavelets3d_"  # the handle API (wt3d.cpp) and the name in messages: StationaryWavelets3D sets its own
+    _cname = "Wavelets3D"
 
     def __init__(self, vol, wname, levels, dtype=None, do_swt=0, do_separable=1, do_cycle_spinning=0):
         if do_swt or not do_separable or do_cycle_spinning:
             raise ValueError("Wavelets3D: only the decimated separable transform is available in 3-D "
                              "(no SWT, non-separable transform or cycle spinning)")
+        self._open(vol, wname, levels, dtype)
+
+    def _open(self, vol, wname, levels, dtype):
+        """Create the C++ instance from a numpy volume or a device tensor (what both volume classes do after checking their arguments)."""
         N.require_gpu()
         dev = _device_source(vol)
         if dev is not None:
@@ -39,18 +44,20 @@ class Wavelets3D(_BandStatsAPI):
             self._keep = np.ascontiguousarray(vol, dtype=dt)
             shape, src, on_host = self._keep.shape, self._keep.ctypes.data_as(C.c_void_p), 1
         if len(shape) != 3:
-            raise ValueError("Wavelets3D needs a 3-D volume (Nz, Nr, Nc)")
+            raise ValueError("%s needs a 3-D volume (Nz, Nr, Nc)" % self._cname)
         self.dtype, self.shape, self.wname = np.dtype(dt), tuple(int(v) for v in shape), wname
         self._L = N.host(self.dtype)
         self._ct = C.c_float if self.dtype == np.float32 else C.c_double
-        self._h = self._L.pdwt_wavelets3d_new(src, self.shape[0], self.shape[1], self.shape[2], wname.encode(), int(levels), on_host)
+        self._h = self._fn("new")(src, self.shape[0], self.shape[1], self.shape[2], wname.encode(), int(levels), on_host)
         self._keep = None
         if not self._h:
-            raise MemoryError("Wavelets3D allocation failed")
+            raise MemoryError("%s allocation failed" % self._cname)
+
+    _fn = _BandStatsAPI._bs  # handle function ``name`` of this class: getattr(self._L, self._hpfx + name)
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.pdwt_wavelets3d_delete(self._h)
+            self._fn("delete")(self._h)
         self._h = None
 
     __del__ = close
@@ -59,7 +66,7 @@ class Wavelets3D(_BandStatsAPI):
     @property
     def info(self):
         i = N.Info3D()
-        self._L.pdwt_wavelets3d_info(self._h, C.byref(i))
+        self._fn("info")(self._h, C.byref(i))
         return i
 
     @property
@@ -68,15 +75,15 @@ class Wavelets3D(_BandStatsAPI):
 
     @property
     def state(self):
-        return self._L.pdwt_wavelets3d_state(self._h)
+        return self._fn("state")(self._h)
 
     @property
     def nbands(self):
-        return self._L.pdwt_wavelets3d_num_bands(self._h)
+        return self._fn("num_bands")(self._h)
 
     def band_shape(self, num):
         z, r, c = C.c_int(), C.c_int(), C.c_int()
-        if self._L.pdwt_wavelets3d_band_shape(self._h, int(num), C.byref(z), C.byref(r), C.byref(c)) <= 0:
+        if self._fn("band_shape")(self._h, int(num), C.byref(z), C.byref(r), C.byref(c)) <= 0:
             raise IndexError(num)
         return z.value, r.value, c.value
 
@@ -89,23 +96,23 @@ class Wavelets3D(_BandStatsAPI):
 
     # -- transforms and coefficient utilities -----------------------------------------------
     def forward(self):
-        self._L.pdwt_wavelets3d_forward(self._h)
+        self._fn("forward")(self._h)
 
     def inverse(self):
-        self._L.pdwt_wavelets3d_inverse(self._h)
+        self._fn("inverse")(self._h)
 
     def soft_threshold(self, beta, do_thresh_appcoeffs=0, normalize=0):
-        self._L.pdwt_wavelets3d_soft_threshold(self._h, self._ct(beta), int(do_thresh_appcoeffs), int(normalize))
+        self._fn("soft_threshold")(self._h, self._ct(beta), int(do_thresh_appcoeffs), int(normalize))
 
     def hard_threshold(self, beta, do_thresh_appcoeffs=0, normalize=0):
-        self._L.pdwt_wavelets3d_hard_threshold(self._h, self._ct(beta), int(do_thresh_appcoeffs), int(normalize))
+        self._fn("hard_threshold")(self._h, self._ct(beta), int(do_thresh_appcoeffs), int(normalize))
 
     def norm1(self):
-        return self.dtype.type(self._L.pdwt_wavelets3d_norm1(self._h))
+        return self.dtype.type(self._fn("norm1")(self._h))
 
     def norm1_f64(self):
         """Sum of |c| over all bands, in double."""
-        return float(self._L.pdwt_wavelets3d_norm1_f64(self._h))
+        return float(self._fn("norm1_f64")(self._h))
 
     def _refuse(self, name):
         raise ValueError("Wavelets3D: %s is not available in 3-D" % name)
@@ -127,7 +134,7 @@ class Wavelets3D(_BandStatsAPI):
     # -- data in and out ---------------------------------------------------------------------
     def get_image(self):
         out = np.empty(self.shape, dtype=self.dtype)
-        n = self._L.pdwt_wavelets3d_get_image(self._h, out.ctypes.data_as(C.c_void_p))
+        n = self._fn("get_image")(self._h, out.ctypes.data_as(C.c_void_p))
         if n != min(out.size, 2**31 - 1):
             raise RuntimeError("get_image failed")
         return out
@@ -141,16 +148,16 @@ class Wavelets3D(_BandStatsAPI):
             vol, mem_is_on_device = dev[0], 1
         if mem_is_on_device:
             _sync_producer()
-            self._L.pdwt_wavelets3d_set_image(self._h, C.c_void_p(int(vol)), 1)
+            self._fn("set_image")(self._h, C.c_void_p(int(vol)), 1)
         else:
             a = np.ascontiguousarray(vol, dtype=self.dtype)
             if a.size != n:
                 raise ValueError("volume of the wrong size")
-            self._L.pdwt_wavelets3d_set_image(self._h, a.ctypes.data_as(C.c_void_p), 0)
+            self._fn("set_image")(self._h, a.ctypes.data_as(C.c_void_p), 0)
 
     def get_coeff(self, num):
         out = np.empty(self.band_shape(num), dtype=self.dtype)
-        n = self._L.pdwt_wavelets3d_get_coeff(self._h, out.ctypes.data_as(C.c_void_p), int(num))
+        n = self._fn("get_coeff")(self._h, out.ctypes.data_as(C.c_void_p), int(num))
         if n != min(out.size, 2**31 - 1):
             raise RuntimeError("get_coeff(%d) failed (state=%d)" % (num, self.state))
         return out
@@ -163,12 +170,12 @@ class Wavelets3D(_BandStatsAPI):
             if dev[2] != self.dtype or int(np.prod(dev[1])) != n:
                 raise ValueError("device band of the wrong dtype or size")
             _sync_producer()
-            self._L.pdwt_wavelets3d_set_coeff(self._h, C.c_void_p(dev[0]), int(num), 1)
+            self._fn("set_coeff")(self._h, C.c_void_p(dev[0]), int(num), 1)
             return
         a = np.ascontiguousarray(arr, dtype=self.dtype)
         if a.size != n:
             raise ValueError("band of the wrong size")
-        self._L.pdwt_wavelets3d_set_coeff(self._h, a.ctypes.data_as(C.c_void_p), int(num), 0)
+        self._fn("set_coeff")(self._h, a.ctypes.data_as(C.c_void_p), int(num), 0)
 
     @property
     def coeffs(self):
@@ -178,10 +185,10 @@ class Wavelets3D(_BandStatsAPI):
         return N.hip().pdwt_sync()
 
     def image_int_ptr(self):
-        return self._L.pdwt_wavelets3d_image_int_ptr(self._h)
+        return self._fn("image_int_ptr")(self._h)
 
     def coeff_int_ptr(self, num):
-        return self._L.pdwt_wavelets3d_coeff_int_ptr(self._h, int(num))
+        return self._fn("coeff_int_ptr")(self._h, int(num))
 
     def image_view(self):
         """The volume as a zero-copy DeviceArray (call ``sync()`` before a consumer on another stream reads it)."""
