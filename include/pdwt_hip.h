@@ -421,6 +421,31 @@ int pdwt_bandlist_stats_f64(const double* const* d_ptr, const size_t* n, int nb,
 int pdwt_bandlist_thresh_f32(int op, float* const* d_ptr, const size_t* n, const float* beta, int nb);
 int pdwt_bandlist_thresh_f64(int op, double* const* d_ptr, const size_t* n, const double* beta, int nb);
 
+/* ---------------------------------------------------------------------------------------------
+ * Band statistics and per-band thresholds over a REGULAR BATCH (pdwt_amd/csrc/bandbatch.hip): B images with the same nb <= 97
+ * bands, band k of n[k] elements in every image.  d_ptr is a table of B * nb band pointers IN DEVICE MEMORY (band k of image b at
+ * d_ptr[b * nb + k]; the caller builds it once and keeps it); n, want_median, beta and out are host arrays, read before the entry
+ * returns (they go through a pinned staging buffer of the library: the caller may free them at once).  Band sizes, block layout
+ * and betas reach the kernels through device memory, never through kernel arguments.  The number of launches and of copies to
+ * the host is fixed per group (up to 8192 / nb images; a larger batch runs group after group) and does not depend on B inside a
+ * group, with one exception: medians of bands of more than 2^19 elements are selected in rounds of 64 (image, band) pairs.
+ *
+ * The stats entries fill out[b * nb + k] with what pdwt_bandlist_stats_* gives for band k of image b, bit for bit in n, max |c|
+ * and the median; want_median[k] (0 moments only, 1 moments and median, 2 the median alone; NULL: no median) holds for band k of
+ * every image.  Sums are accumulated in double and combined in a fixed order (no float atomics: two runs give the same bits).
+ * Launches: moments + combine, ONE selection launch for all asking bands of up to 2^19 elements (every radix pass inside it), and
+ * for larger asking bands 3 (float) / 6 (double) histogram + pick launch pairs per round of 64 (image, band) pairs.  They
+ * SYNCHRONISE (one copy to the host per group).
+ *
+ * The thresh entries apply op (0 soft, 1 hard) with beta[b * nb + k] to band k of image b, in place, in one launch per group;
+ * beta < 0 leaves that band of that image alone.  The kernel runs asynchronously; beta has been consumed when the entry returns.
+ * B < 1, nb < 1, nb > 97, a NULL d_ptr / n / out / beta or an unknown op: PDWT_EINVAL.
+ * --------------------------------------------------------------------------------------------- */
+int pdwt_bandbatch_stats_f32(const float* const* d_ptr, const size_t* n, int B, int nb, const unsigned char* want_median, pdwt_band_stats* out);
+int pdwt_bandbatch_stats_f64(const double* const* d_ptr, const size_t* n, int B, int nb, const unsigned char* want_median, pdwt_band_stats* out);
+int pdwt_bandbatch_thresh_f32(int op, float* const* d_ptr, const size_t* n, const float* beta, int B, int nb);
+int pdwt_bandbatch_thresh_f64(int op, double* const* d_ptr, const size_t* n, const double* beta, int B, int nb);
+
 #ifdef __cplusplus
 }
 #endif

@@ -152,6 +152,7 @@ class Wavelets {
     double denoise(int method, double sigma = -1.0, int kind = 0, DTYPE* betas_out = NULL);
 
   private:
+    friend struct WaveletsImagesOps; /* ADDITION: the batch statistics of wt_batch.h (wt.cpp) need the device and the norm bookkeeping of the members */
     /* per-instance filter bank (the reference keeps it in process-global constant memory, so two
      * live instances silently share the last one's taps -- SURVEY.md Appendix B-1).  Appended after
      * the public members so their offsets match the reference layout. */

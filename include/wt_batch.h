@@ -157,6 +157,14 @@ class WaveletsBatch {
 #define WB_INVERSE pdwt_batch2d_inverse_f32
 #define WB_DESTROY pdwt_batch2d_destroy
 #endif
+/* The host half of the batch statistics below (libpdwt / libpdwtd: pdwt_amd/csrc/wt.cpp, bandstats_host.hpp; kernels: bandbatch.hip).
+ * img: the B members; *table: the device table of their band pointers, built on the first call and owned by the caller (pdwt_free). */
+int w_images_all_band_stats(Wavelets* const* img, int B, void** table, w_band_stats* out, int with_median);
+int w_images_estimate_sigma(Wavelets* const* img, int B, void** table, double* sigma_out);
+int w_images_threshold_bands(Wavelets* const* img, int B, void** table, const DTYPE* betas, int kind);
+int w_images_denoise(Wavelets* const* img, int B, void** table, int method, const double* sigma_in, int kind, double* sigma_out, DTYPE* betas_out);
+int w_images_norm1(Wavelets* const* img, int B, void** table, double* out);
+
 class WaveletsImages {
   public:
     std::vector<Wavelets*> img;
@@ -164,7 +172,7 @@ class WaveletsImages {
 
     /* imgs: B contiguous Nr x Nc images (host, or device when memisonhost = 0); do_swt = 1: the undecimated transform (one launch per level
      * over all images in the float build when every level is inside the fused SWT level kernels; image after image otherwise) */
-    WaveletsImages(DTYPE* imgs, int B, int Nr_, int Nc_, const char* wname, int levels, int memisonhost = 1, int do_swt = 0) : Nr(Nr_), Nc(Nc_), batch_(NULL)
+    WaveletsImages(DTYPE* imgs, int B, int Nr_, int Nc_, const char* wname, int levels, int memisonhost = 1, int do_swt = 0) : Nr(Nr_), Nc(Nc_), batch_(NULL), table_(NULL)
     {
         for (int b = 0; b < B; b++) {
             img.push_back(new Wavelets(imgs + (size_t)b * Nr * Nc, Nr, Nc, wname, levels, memisonhost, 1, 0, do_swt, 2));
@@ -194,6 +202,7 @@ class WaveletsImages {
     ~WaveletsImages()
     {
         if (batch_) WB_DESTROY(batch_);
+        if (table_) pdwt_free(table_);
         for (size_t b = 0; b < img.size(); b++) delete img[b];
     }
     bool ok() const
@@ -236,9 +245,40 @@ class WaveletsImages {
         return n;
     }
 
+    /* Band statistics and noise-adaptive thresholds of ALL images (the methods of Wavelets, include/wt.h, over the batch): a number of
+     * launches and ONE copy to the host that do not depend on the number of images, instead of img.size() blocking calls.  They only
+     * need the band pointers: they work whether or not the transform is batched(), and for do_swt = 1.  Arrays are image-major: entry
+     * b * num_bands() + k belongs to band k of image b.  EVERY member must hold valid coefficients (after forward(), before inverse());
+     * otherwise nothing is launched and a negative value is returned.  On success 0; the members' states stay as the per-image methods
+     * leave them, a failed threshold sets W_THRESHOLD_ERROR on every member.
+     *   all_band_stats   Wavelets::all_band_stats of every image (out: B * num_bands() entries)
+     *   estimate_sigma   every image's OWN sigma: median |its finest diagonal band| / 0.6744897501960817 (sigma_out: B values)
+     *   threshold_bands  betas: B * num_bands(); beta < 0 leaves that band of that image alone; kind 0 soft, 1 hard
+     *   denoise          Wavelets::denoise of every image with its own sigma: sigma_in NULL, or B values of which a negative one is
+     *                    estimated from its image; the sigmas used go to sigma_out (B), the betas (band 0 = -1) to betas_out (B * num_bands()
+     *                    or NULL).  The betas come from the rule of Wavelets::denoise: VisuShrink betas are the per-image ones bit for bit.
+     *   norm1            sum |c| over the bands of each image, in double (out: B values)
+     * The first of these calls records the members' band pointers in a device table that later calls reuse: `img` must not be
+     * resized, reordered or have members replaced afterwards (set_image / set_coeff / forward on a member are fine: bands do not move). */
+    int num_bands() const { return img.empty() ? 0 : pdwt_num_bands(info_of(img[0]->winfos)); }
+    int all_band_stats(w_band_stats* out, int with_median = 0) { return w_images_all_band_stats(img.data(), (int)img.size(), &table_, out, with_median); }
+    int estimate_sigma(double* sigma_out) { return w_images_estimate_sigma(img.data(), (int)img.size(), &table_, sigma_out); }
+    int threshold_bands(const DTYPE* betas, int kind = 0) { return w_images_threshold_bands(img.data(), (int)img.size(), &table_, betas, kind); }
+    int denoise(int method, const double* sigma_in, int kind, double* sigma_out, DTYPE* betas_out = NULL)
+    {
+        return w_images_denoise(img.data(), (int)img.size(), &table_, method, sigma_in, kind, sigma_out, betas_out);
+    }
+    int norm1(double* out) { return w_images_norm1(img.data(), (int)img.size(), &table_, out); }
+
   private:
     void* batch_;
+    void* table_; /* device: the B * num_bands() band pointers (built by the first statistics call, kept: no method moves a band) */
     WB_FILTERS bank_;
+    static pdwt_info info_of(const w_info& w)
+    {
+        pdwt_info info = {w.ndims, w.Nr, w.Nc, w.nlevels, w.do_swt, w.hlen};
+        return info;
+    }
     WaveletsImages(const WaveletsImages&);
     WaveletsImages& operator=(const WaveletsImages&);
 };

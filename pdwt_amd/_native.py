@@ -64,7 +64,7 @@ TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coe
                   "forward_swt_nonseparable", "inverse_swt_nonseparable",
                   "create_coeffs_buffer3d", "free_coeffs_buffer3d", "forward3d_separable", "inverse3d_separable", "soft_thresh3d", "hard_thresh3d",
                   "norm1_3d", "create_coeffs_buffer_swt3d", "free_coeffs_buffer_swt3d", "forward3d_swt", "inverse3d_swt",
-                  "soft_thresh_swt3d", "hard_thresh_swt3d", "norm1_swt3d", "bandlist_stats", "bandlist_thresh"] + DRIVERS + HAAR_DRIVERS)
+                  "soft_thresh_swt3d", "hard_thresh_swt3d", "norm1_swt3d", "bandlist_stats", "bandlist_thresh", "bandbatch_stats", "bandbatch_thresh"] + DRIVERS + HAAR_DRIVERS)
 
 _hip = None
 _host = {}
@@ -187,6 +187,9 @@ def hip():
         getattr(L, "pdwt_norm1_swt3d_" + sfx).argtypes = [PP, Info3D, C.POINTER(C.c_double)]
         getattr(L, "pdwt_bandlist_stats_" + sfx).argtypes = [PP, C.POINTER(sz), ci, C.POINTER(C.c_ubyte), C.POINTER(BandStats)]
         getattr(L, "pdwt_bandlist_thresh_" + sfx).argtypes = [ci, PP, C.POINTER(sz), P, ci]
+        # the same over a regular batch: the table of B * nb band pointers is a DEVICE address
+        getattr(L, "pdwt_bandbatch_stats_" + sfx).argtypes = [vp, C.POINTER(sz), ci, ci, C.POINTER(C.c_ubyte), C.POINTER(BandStats)]
+        getattr(L, "pdwt_bandbatch_thresh_" + sfx).argtypes = [ci, vp, C.POINTER(sz), P, ci, ci]
     _hip = L
     return L
 
@@ -248,6 +251,12 @@ def host(dtype):
         L.pdwt_images_at.argtypes = [vp, ci]
         for n in ("delete", "ok", "batched", "forward", "inverse"):
             getattr(L, "pdwt_images_" + n).argtypes = [vp]
+        L.pdwt_images_num_bands.argtypes = [vp]
+        L.pdwt_images_all_band_stats.argtypes = [vp, C.POINTER(BandStats), ci]
+        L.pdwt_images_estimate_sigma.argtypes = [vp, C.POINTER(C.c_double)]
+        L.pdwt_images_threshold_bands.argtypes = [vp, vp, ci]
+        L.pdwt_images_denoise.argtypes = [vp, ci, C.POINTER(C.c_double), ci, C.POINTER(C.c_double), vp]
+        L.pdwt_images_norm1.argtypes = [vp, C.POINTER(C.c_double)]
         L.pdwt_wavelets_coeff_int_ptr.restype = C.c_ssize_t
         L.pdwt_wavelets_coeff_int_ptr.argtypes = [vp, ci]
         # Wavelets3D (include/wt3d.h) and StationaryWavelets3D (include/swt3d.h), both in wt3d.cpp: the same handle API

@@ -16,6 +16,7 @@
 
 #include "../../include/pdwt_hip.h"
 #include "../../include/wt.h"
+#include "../../include/wt_batch.h"
 #include "bandstats_host.hpp"
 
 static_assert(sizeof(w_info) == sizeof(pdwt_info), "w_info must mirror pdwt_info");
@@ -674,6 +675,126 @@ double Wavelets::denoise(int method, double sigma, int kind, DTYPE* betas_out)
     }
     if (betas_out) memcpy(betas_out, betas, (size_t)bl.nb * sizeof(DTYPE));
     return sigma;
+}
+
+// ---- the same over a batch of equally sized instances on one device (ADDITIONS, include/wt_batch.h: WaveletsImages) ----
+// Every call checks that ALL members hold valid coefficients (otherwise nothing is launched), runs a number of launches and one
+// copy to the host that do not depend on the number of images (bandbatch.hip), and leaves the members' states as the per-image
+// methods above leave them: unchanged on success, W_THRESHOLD_ERROR when a threshold failed.
+struct WaveletsImagesOps {
+    // the band geometry of the batch (ptr[] = the bands of image 0); nb = 0: a member without valid coefficients, or of another geometry
+    static pdwt_bl::BandList geometry(Wavelets* const* img, int B)
+    {
+        pdwt_bl::BandList g;
+        g.nb = 0;
+        if (!img || B < 1 || !img[0]) return g;
+        g = band_list(*img[0]);
+        for (int b = 1; b < B && g.nb; b++) {
+            const bool same = img[b] && memcmp(&img[b]->winfos, &img[0]->winfos, sizeof(w_info)) == 0;
+            if (!same || band_list(*img[b]).nb != g.nb) g.nb = 0;
+        }
+        return g;
+    }
+    // the B * nb band pointers in device memory, built on first use and kept in *table: set_coeff() copies INTO the bands, no method moves them
+    static DTYPE* const* table(Wavelets* const* img, int B, int nb, void** table)
+    {
+        if (!table) return NULL;
+        if (!*table) {
+            DTYPE** host = new DTYPE*[(size_t)B * nb];
+            for (int b = 0; b < B; b++)
+                for (int k = 0; k < nb; k++) host[(size_t)b * nb + k] = img[b]->d_coeffs[k];
+            void* d = pdwt_malloc((size_t)B * nb * sizeof(DTYPE*));
+            if (d && pdwt_memcpy_h2d(d, host, (size_t)B * nb * sizeof(DTYPE*)) != PDWT_OK) {
+                pdwt_free(d);
+                d = NULL;
+            }
+            delete[] host;
+            *table = d;
+        }
+        return (DTYPE* const*)*table;
+    }
+    static void changed(Wavelets* const* img, int B, int rc, const char* where)
+    {
+        if (rc != PDWT_OK) report(where, rc);
+        for (int b = 0; b < B; b++) {
+            coeffs_changed(img[b]->filters_);  // a cached sum |c| would be stale
+            if (rc != PDWT_OK) img[b]->state = W_THRESHOLD_ERROR;
+        }
+    }
+    static const void* dev_of(Wavelets* const* img, int B) { return (img && B > 0 && img[0]) ? img[0]->filters_ : NULL; }
+};
+
+int w_images_all_band_stats(Wavelets* const* img, int B, void** table, w_band_stats* out, int with_median)
+{
+    DevScope dev_scope_(WaveletsImagesOps::dev_of(img, B));
+    const pdwt_bl::BandList g = WaveletsImagesOps::geometry(img, B);
+    if (!g.nb || !out) return PDWT_EINVAL;
+    DTYPE* const* tab = WaveletsImagesOps::table(img, B, g.nb, table);
+    if (!tab) return PDWT_ENOMEM;
+    const int rc = pdwt_bl::batch_stats(g, tab, B, out, with_median);
+    if (rc != PDWT_OK) report("WaveletsImages::all_band_stats()", rc);
+    return rc;
+}
+
+int w_images_estimate_sigma(Wavelets* const* img, int B, void** table, double* sigma_out)
+{
+    DevScope dev_scope_(WaveletsImagesOps::dev_of(img, B));
+    const pdwt_bl::BandList g = WaveletsImagesOps::geometry(img, B);
+    if (!g.nb || !sigma_out) return PDWT_EINVAL;
+    DTYPE* const* tab = WaveletsImagesOps::table(img, B, g.nb, table);
+    if (!tab) return PDWT_ENOMEM;
+    pdwt_band_stats* s = new pdwt_band_stats[(size_t)B * g.nb];
+    const int rc = pdwt_bl::batch_estimate_sigma(g, tab, B, s, sigma_out);
+    delete[] s;
+    if (rc != PDWT_OK) report("WaveletsImages::estimate_sigma()", rc);
+    return rc;
+}
+
+int w_images_threshold_bands(Wavelets* const* img, int B, void** table, const DTYPE* betas, int kind)
+{
+    DevScope dev_scope_(WaveletsImagesOps::dev_of(img, B));
+    const pdwt_bl::BandList g = WaveletsImagesOps::geometry(img, B);
+    if (!g.nb || !betas || (kind != 0 && kind != 1)) return PDWT_EINVAL;
+    DTYPE* const* tab = WaveletsImagesOps::table(img, B, g.nb, table);
+    if (!tab) return PDWT_ENOMEM;
+    const int rc = pdwt_bl::batch_threshold(g, tab, B, betas, kind);
+    WaveletsImagesOps::changed(img, B, rc, "WaveletsImages::threshold_bands()");
+    return rc;
+}
+
+int w_images_denoise(Wavelets* const* img, int B, void** table, int method, const double* sigma_in, int kind, double* sigma_out, DTYPE* betas_out)
+{
+    DevScope dev_scope_(WaveletsImagesOps::dev_of(img, B));
+    const pdwt_bl::BandList g = WaveletsImagesOps::geometry(img, B);
+    if (!g.nb || !sigma_out || (method != 0 && method != 1) || (kind != 0 && kind != 1)) return PDWT_EINVAL;
+    DTYPE* const* tab = WaveletsImagesOps::table(img, B, g.nb, table);
+    if (!tab) return PDWT_ENOMEM;
+    pdwt_band_stats* s = new pdwt_band_stats[(size_t)B * g.nb];
+    DTYPE* betas = betas_out ? betas_out : new DTYPE[(size_t)B * g.nb];
+    const int rc = pdwt_bl::batch_denoise(g, tab, B, method, kind, sigma_in, s, sigma_out, betas);
+    if (!betas_out) delete[] betas;
+    delete[] s;
+    WaveletsImagesOps::changed(img, B, rc, "WaveletsImages::denoise()");
+    return rc;
+}
+
+int w_images_norm1(Wavelets* const* img, int B, void** table, double* out)
+{
+    DevScope dev_scope_(WaveletsImagesOps::dev_of(img, B));
+    const pdwt_bl::BandList g = WaveletsImagesOps::geometry(img, B);
+    if (!g.nb || !out) return PDWT_EINVAL;
+    DTYPE* const* tab = WaveletsImagesOps::table(img, B, g.nb, table);
+    if (!tab) return PDWT_ENOMEM;
+    w_band_stats* s = new w_band_stats[(size_t)B * g.nb];
+    const int rc = pdwt_bl::batch_stats(g, tab, B, s, 0);
+    for (int b = 0; b < B && rc == PDWT_OK; b++) {
+        double acc = 0.0;
+        for (int k = 0; k < g.nb; k++) acc += s[(size_t)b * g.nb + k].sum_abs;
+        out[b] = acc;
+    }
+    delete[] s;
+    if (rc != PDWT_OK) report("WaveletsImages::norm1()", rc);
+    return rc;
 }
 
 // src/wt.cu:364-366: if inplace = 1 the result is in d_image, otherwise in d_tmp

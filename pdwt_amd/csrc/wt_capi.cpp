@@ -85,4 +85,14 @@ int pdwt_images_batched(void* h) { return static_cast<WaveletsImages*>(h)->batch
 void pdwt_images_forward(void* h) { static_cast<WaveletsImages*>(h)->forward(); }
 void pdwt_images_inverse(void* h) { static_cast<WaveletsImages*>(h)->inverse(); }
 void* pdwt_images_at(void* h, int b) { return static_cast<WaveletsImages*>(h)->img[(size_t)b]; } /* borrowed: owned by the batch */
+/* band statistics and noise-adaptive thresholds of all images at once (include/wt_batch.h); arrays are image-major */
+int pdwt_images_num_bands(void* h) { return static_cast<WaveletsImages*>(h)->num_bands(); }
+int pdwt_images_all_band_stats(void* h, w_band_stats* out, int with_median) { return static_cast<WaveletsImages*>(h)->all_band_stats(out, with_median); }
+int pdwt_images_estimate_sigma(void* h, double* sigma_out) { return static_cast<WaveletsImages*>(h)->estimate_sigma(sigma_out); }
+int pdwt_images_threshold_bands(void* h, const DTYPE* betas, int kind) { return static_cast<WaveletsImages*>(h)->threshold_bands(betas, kind); }
+int pdwt_images_denoise(void* h, int method, const double* sigma_in, int kind, double* sigma_out, DTYPE* betas_out)
+{
+    return static_cast<WaveletsImages*>(h)->denoise(method, sigma_in, kind, sigma_out, betas_out);
+}
+int pdwt_images_norm1(void* h, double* out) { return static_cast<WaveletsImages*>(h)->norm1(out); }
 }

@@ -427,6 +427,86 @@ class ImageBatch:
     def get_images(self):
         return np.stack([self[b].get_image() for b in range(self.shape[0])])
 
+    # ---- band statistics and noise-adaptive thresholds of ALL images (include/wt_batch.h; kernels: bandbatch.hip): the methods of
+    # _BandStatsAPI over the batch, in a fixed number of launches and ONE copy to the host per group of images, not per image.
+    # Every image needs valid coefficients (after forward(), before inverse()): RuntimeError otherwise, and nothing is touched.
+    @property
+    def nbands(self):
+        return int(self._L.pdwt_images_num_bands(self._h))
+
+    def _refused(self, what, rc=-1):
+        if rc != -1:  # (PDWT_EINVAL is the refusal; anything else is a device error: allocation, copy or launch)
+            return RuntimeError("%s failed on the device (code %d): %s" % (what, rc, (N.hip().pdwt_last_error_string() or b"").decode()))
+        return RuntimeError("%s refused (states=%s): the coefficients of every image must be valid"
+                            % (what, sorted({self[b].state for b in range(self.shape[0])})))
+
+    def all_band_stats(self, with_median=False):
+        """{n, sum_abs, sum_sq, max_abs, median_abs}: float64 arrays of shape (B, nbands), entry [b, k] = ``batch[b].band_stats(k)``
+        (``median_abs`` NaN unless ``with_median``)."""
+        B, nb = self.shape[0], self.nbands
+        out = (N.BandStats * (B * max(nb, 1)))()
+        rc = self._L.pdwt_images_all_band_stats(self._h, out, int(bool(with_median)))
+        if rc != 0:
+            raise self._refused("all_band_stats", rc)
+        a = np.frombuffer(out, dtype=np.float64).reshape(B, max(nb, 1), len(N.BandStats._fields_))[:, :nb]
+        return {k: a[:, :, i].copy() for i, (k, _) in enumerate(N.BandStats._fields_)}
+
+    def estimate_sigma(self):
+        """(B,) float64: every image's OWN noise level, median |its finest diagonal band| / 0.6744897501960817."""
+        s = np.zeros(self.shape[0], dtype=np.float64)
+        rc = self._L.pdwt_images_estimate_sigma(self._h, s.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != 0:
+            raise self._refused("estimate_sigma", rc)
+        return s
+
+    def threshold_bands(self, betas, kind="soft"):
+        """``betas``: (B, nbands), or (nbands,) for every image; a negative beta leaves that band of that image alone."""
+        if kind not in _BandStatsAPI.KINDS:
+            raise ValueError("kind must be 'soft' or 'hard'")
+        B, nb = self.shape[0], self.nbands
+        b = np.asarray(betas, dtype=self.dtype)
+        if b.shape == (nb,):
+            b = np.broadcast_to(b, (B, nb))
+        if b.shape != (B, nb):
+            raise ValueError("betas of shape %s for %d images of %d bands" % (b.shape, B, nb))
+        b = np.ascontiguousarray(b)
+        rc = self._L.pdwt_images_threshold_bands(self._h, b.ctypes.data_as(C.c_void_p), _BandStatsAPI.KINDS[kind])
+        if rc != 0:
+            raise self._refused("threshold_bands", rc)
+
+    def denoise(self, method="bayes", sigma=None, kind="soft"):
+        """``Wavelets.denoise`` of every image, each with its own sigma: ``sigma`` None (estimated per image), a scalar or a (B,) array.
+        Returns {"sigma": (B,) float64, "betas": (B, nbands) in the batch's dtype, betas[:, 0] == -1}."""
+        if method not in _BandStatsAPI.METHODS:
+            raise ValueError("method must be 'visu' or 'bayes'")
+        if kind not in _BandStatsAPI.KINDS:
+            raise ValueError("kind must be 'soft' or 'hard'")
+        B, nb = self.shape[0], self.nbands
+        sin = None
+        if sigma is not None:
+            sin = np.asarray(sigma, dtype=np.float64)
+            if sin.shape not in ((), (B,)):
+                raise ValueError("sigma must be None, a scalar or %d values" % B)
+            sin = np.ascontiguousarray(np.broadcast_to(sin, (B,)))
+            if not np.all(sin >= 0):
+                raise ValueError("sigma must be >= 0 (None: estimated)")
+        sout = np.zeros(B, dtype=np.float64)
+        betas = np.zeros((B, max(nb, 1)), dtype=self.dtype)
+        dp = C.POINTER(C.c_double)
+        rc = self._L.pdwt_images_denoise(self._h, _BandStatsAPI.METHODS[method], sin.ctypes.data_as(dp) if sin is not None else None,
+                                         _BandStatsAPI.KINDS[kind], sout.ctypes.data_as(dp), betas.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise self._refused("denoise", rc)
+        return {"sigma": sout, "betas": betas[:, :nb]}
+
+    def norm1(self):
+        """(B,) float64: sum |c| over the bands of each image, accumulated in double."""
+        out = np.zeros(self.shape[0], dtype=np.float64)
+        rc = self._L.pdwt_images_norm1(self._h, out.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != 0:
+            raise self._refused("norm1", rc)
+        return out
+
     def sync(self):
         return N.hip().pdwt_sync()
 

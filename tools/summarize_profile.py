@@ -13,7 +13,7 @@ title = sys.argv[3] if len(sys.argv) > 3 else os.path.basename(d)
 
 
 def short(n):
-    n = n.replace("void pdwt::", "").replace("void ", "")
+    n = n.replace("void pdwt::", "").replace("void ", "").replace("pdwt::", "").replace("(anonymous namespace)::", "")
     return n.split("(")[0][:70]
 
 
