@@ -208,6 +208,15 @@ long long pdwt_band_size(pdwt_info info, int num, int* band_Nr, int* band_Nc);
  *   forward_swt_separable[_1d] <- src/separable.cu:496-537
  *   inverse_swt_separable[_1d] <- src/separable.cu:629-672
  *   haar_forward2d/inverse2d/forward1d/inverse1d <- src/haar.cu:61-119,163-221
+ *
+ * Buffers of the caller.  d_image, every band pointer and d_tmp (and the buffers of the 3-D drivers
+ * below) need only be aligned to their element type: the kernels that use 16-byte accesses are
+ * chosen only when every pointer they touch is 16-byte aligned, and a slower kernel with the same
+ * result runs otherwise.  Bands may lie back to back.  d_tmp may hold anything on entry.  A driver
+ * writes only: d_image (inverse); the bands within their sizes (pdwt_band_size; band 0 within its
+ * level-1 allocation; the 1-D / 2-D inverse leaves every band but band 0 intact, the 3-D inverses
+ * leave every band intact); and the first pdwt_tmp_elems(info) elements of d_tmp.  Nothing before or
+ * behind any of these is written (tests/test_cabi_buffers_gpu.py).
  * ------------------------------------------------------------------------------------------- */
 /* test / tuning knobs (not part of the reference seam; names and meaning in INTEGRATION.md).  Each knob is
  * initialised ONCE from its PDWT_<NAME> environment variable and changed at run time only through

@@ -21,10 +21,10 @@ from oracle import oracle as orc
 BAND_KEYS = ("aad", "ada", "add", "daa", "dad", "dda", "ddd")  # restated, not imported: storage order of a level's details
 
 
-def bank(wname, do_swt=0):
-    """(L, H, IL, IH) of a bank as float64 arrays"""
+def bank(wname, do_swt=0, dt=np.float64):
+    """(L, H, IL, IH) of a bank: the float64 taps, rounded to `dt`"""
     _, F, _ = orc.filters(wname, np.float64, do_swt)
-    return tuple(np.asarray(F[k], np.float64) for k in ("L", "H", "IL", "IH"))
+    return tuple(np.asarray(F[k], np.float64).astype(dt) for k in ("L", "H", "IL", "IH"))
 
 
 def _along(vec, ndim, axis):
@@ -35,9 +35,9 @@ def _along(vec, ndim, axis):
 
 
 # ---- one level along an axis ----------------------------------------------------------------------------
-def dwt_ana(x, axis, F):
+def dwt_ana(x, axis, F, dt=np.float64):
     """(lo, hi) of the decimated analysis along `axis`; output length (n + 1) // 2"""
-    x = np.asarray(x, np.float64)
+    x = np.asarray(x, dt)
     FL, FH = F[0], F[1]
     hlen, n = len(FL), x.shape[axis]
     if n & 1:  # repeat the last sample: the extended line has even length
@@ -53,9 +53,9 @@ def dwt_ana(x, axis, F):
     return lo, hi
 
 
-def dwt_syn(a, d, axis, nout, F):
+def dwt_syn(a, d, axis, nout, F, dt=np.float64):
     """the decimated synthesis along `axis` of the low branch a and the high branch d into nout samples"""
-    a, d = np.asarray(a, np.float64), np.asarray(d, np.float64)
+    a, d = np.asarray(a, dt), np.asarray(d, dt)
     IL, IH = F[2], F[3]
     hlen, nin = len(IL), a.shape[axis]
     h2 = hlen // 2
@@ -71,9 +71,9 @@ def dwt_syn(a, d, axis, nout, F):
     return out
 
 
-def swt_ana(x, axis, F, f):
+def swt_ana(x, axis, F, f, dt=np.float64):
     """(lo, hi) of the a-trous analysis along `axis` at tap spacing f"""
-    x = np.asarray(x, np.float64)
+    x = np.asarray(x, dt)
     FL, FH = F[0], F[1]
     hlen, n = len(FL), x.shape[axis]
     c = (hlen // 2 - 1) * f
@@ -86,9 +86,9 @@ def swt_ana(x, axis, F, f):
     return lo, hi
 
 
-def swt_syn(a, d, axis, F, f):
+def swt_syn(a, d, axis, F, f, dt=np.float64):
     """the a-trous synthesis along `axis` at tap spacing f"""
-    a, d = np.asarray(a, np.float64), np.asarray(d, np.float64)
+    a, d = np.asarray(a, dt), np.asarray(d, dt)
     IL, IH = F[2], F[3]
     hlen, n = len(IL), a.shape[axis]
     c = (hlen // 2) * f
@@ -170,45 +170,46 @@ def _level_bands(coeffs, L, lev, a):
     return d
 
 
-def dwt3_forward(vol, wname, L):
-    F = bank(wname, 0)
-    a, per_level = np.asarray(vol, np.float64), []
+def dwt3_forward(vol, wname, L, dt=np.float64):
+    """dt = float32: the same sums with float32 taps, products and accumulators (what a float32 kernel can be held to)"""
+    F = bank(wname, 0, dt)
+    a, per_level = np.asarray(vol, dt), []
     for _ in range(L):
-        b = _ana3(a, lambda v, axis: dwt_ana(v, axis, F))
+        b = _ana3(a, lambda v, axis: dwt_ana(v, axis, F, dt))
         per_level.append([b[k] for k in BAND_KEYS])
         a = b["aaa"]
     return _pack(a, per_level)
 
 
-def dwt3_inverse(coeffs, shape, wname, L):
-    F = bank(wname, 0)
+def dwt3_inverse(coeffs, shape, wname, L, dt=np.float64):
+    F = bank(wname, 0, dt)
     shapes = [tuple(shape)]
     for _ in range(L):
         shapes.append(tuple((s + 1) // 2 for s in shapes[-1]))
     a = coeffs[0]
     for lev in range(L, 0, -1):
         nout = shapes[lev - 1]
-        a = _syn3(_level_bands(coeffs, L, lev, a), lambda lo, hi, axis: dwt_syn(lo, hi, axis, nout[axis], F))
+        a = _syn3(_level_bands(coeffs, L, lev, a), lambda lo, hi, axis: dwt_syn(lo, hi, axis, nout[axis], F, dt))
     return a
 
 
-def swt3_forward(vol, wname, L):
-    F = bank(wname, 1)
-    a, per_level = np.asarray(vol, np.float64), []
+def swt3_forward(vol, wname, L, dt=np.float64):
+    F = bank(wname, 1, dt)
+    a, per_level = np.asarray(vol, dt), []
     for lev in range(1, L + 1):
         f = 2 ** (lev - 1)
-        b = _ana3(a, lambda v, axis: swt_ana(v, axis, F, f))
+        b = _ana3(a, lambda v, axis: swt_ana(v, axis, F, f, dt))
         per_level.append([b[k] for k in BAND_KEYS])
         a = b["aaa"]
     return _pack(a, per_level)
 
 
-def swt3_inverse(coeffs, wname, L):
-    F = bank(wname, 1)
+def swt3_inverse(coeffs, wname, L, dt=np.float64):
+    F = bank(wname, 1, dt)
     a = coeffs[0]
     for lev in range(L, 0, -1):
         f = 2 ** (lev - 1)
-        a = _syn3(_level_bands(coeffs, L, lev, a), lambda lo, hi, axis: swt_syn(lo, hi, axis, F, f))
+        a = _syn3(_level_bands(coeffs, L, lev, a), lambda lo, hi, axis: swt_syn(lo, hi, axis, F, f, dt))
     return a
 
 
