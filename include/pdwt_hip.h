@@ -455,6 +455,31 @@ int pdwt_bandbatch_stats_f64(const double* const* d_ptr, const size_t* n, int B,
 int pdwt_bandbatch_thresh_f32(int op, float* const* d_ptr, const size_t* n, const float* beta, int B, int nb);
 int pdwt_bandbatch_thresh_f64(int op, double* const* d_ptr, const size_t* n, const double* beta, int B, int nb);
 
+/* ---------------------------------------------------------------------------------------------
+ * 2-D wavelet packets (pdwt_amd/csrc/wpt2d.hip; the class: include/wpt.h).  The packet tree decomposes every band again: depth l
+ * holds 4^l nodes of div2^l(Nr) x div2^l(Nc) elements, CONTIGUOUS in one array (node stride = the node's element count); node i has
+ * the children 4i + {0: A, 1: H, 2: V, 3: D} at depth l + 1 -- the bands of the one-level 2-D transform of the drivers above
+ * (periodised; the same arithmetic, the same meaning of H and V), for hlen == 2 the clamped 2x2 butterfly of the Haar drivers.
+ *
+ * The level entries run ONE depth step in ONE launch (one workgroup per tile and node).  d_parent: the array of depth l, nodes of
+ * nr x nc elements; d_child: the array of depth l + 1, nodes of div2(nr) x div2(nc) elements.  d_nodes: DEVICE array of nnodes
+ * parent indices, or NULL for the parents 0 .. nnodes-1.  forward reads parent d_nodes[k] and writes its four children
+ * 4 * d_nodes[k] + 0..3; inverse reads those children and writes that parent; nothing else is touched, so a partial basis costs
+ * work only on the parents named.  1 <= nnodes <= 16384 (a grid dimension), nr * nc < 2^31, an even f->hlen of 2 .. 40 and, for
+ * hlen > 2, nr >= hlen and nc >= hlen, and at most 65535 rows of tiles (nr <= 262140 for hlen == 2, else about 2^21); anything else, or a NULL d_parent / d_child / f, is PDWT_EINVAL and nothing is launched.
+ * Buffers need only be aligned to their element type.  Asynchronous on the library stream.
+ *
+ * node_cost: an additive cost of each of nnodes (<= 65535) contiguous nodes of node_elems elements in one launch, out[i] on the HOST:
+ * kind 0 = sum |c| ("l1"), kind 1 = -sum c^2 ln c^2 over the non-zero c ("shannon").  Accumulated in double and combined in a
+ * fixed order (no atomics: two runs give the same bits).  SYNCHRONISES.
+ * ------------------------------------------------------------------------------------------- */
+int pdwt_wpt2d_forward_level_f32(const float* d_parent, float* d_child, int nr, int nc, const int* d_nodes, int nnodes, const pdwt_filters_f32* f);
+int pdwt_wpt2d_forward_level_f64(const double* d_parent, double* d_child, int nr, int nc, const int* d_nodes, int nnodes, const pdwt_filters_f64* f);
+int pdwt_wpt2d_inverse_level_f32(float* d_parent, const float* d_child, int nr, int nc, const int* d_nodes, int nnodes, const pdwt_filters_f32* f);
+int pdwt_wpt2d_inverse_level_f64(double* d_parent, const double* d_child, int nr, int nc, const int* d_nodes, int nnodes, const pdwt_filters_f64* f);
+int pdwt_wpt2d_node_cost_f32(const float* d_nodes, size_t node_elems, int nnodes, int kind, double* out);
+int pdwt_wpt2d_node_cost_f64(const double* d_nodes, size_t node_elems, int nnodes, int kind, double* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -18,6 +18,11 @@ class Info3D(C.Structure):
     _fields_ = [("Nz", C.c_int), ("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int)]
 
 
+class InfoWPT(C.Structure):
+    """== w_info_wpt (include/wpt.h)."""
+    _fields_ = [("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int)]
+
+
 class BandStats(C.Structure):
     """== pdwt_band_stats (include/pdwt_hip.h) == w_band_stats (include/wt.h)."""
     _fields_ = [("n", C.c_double), ("sum_abs", C.c_double), ("sum_sq", C.c_double), ("max_abs", C.c_double), ("median_abs", C.c_double)]
@@ -64,7 +69,8 @@ TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coe
                   "forward_swt_nonseparable", "inverse_swt_nonseparable",
                   "create_coeffs_buffer3d", "free_coeffs_buffer3d", "forward3d_separable", "inverse3d_separable", "soft_thresh3d", "hard_thresh3d",
                   "norm1_3d", "create_coeffs_buffer_swt3d", "free_coeffs_buffer_swt3d", "forward3d_swt", "inverse3d_swt",
-                  "soft_thresh_swt3d", "hard_thresh_swt3d", "norm1_swt3d", "bandlist_stats", "bandlist_thresh", "bandbatch_stats", "bandbatch_thresh"] + DRIVERS + HAAR_DRIVERS)
+                  "soft_thresh_swt3d", "hard_thresh_swt3d", "norm1_swt3d", "bandlist_stats", "bandlist_thresh", "bandbatch_stats", "bandbatch_thresh",
+                  "wpt2d_forward_level", "wpt2d_inverse_level", "wpt2d_node_cost"] + DRIVERS + HAAR_DRIVERS)
 
 _hip = None
 _host = {}
@@ -190,6 +196,10 @@ def hip():
         # the same over a regular batch: the table of B * nb band pointers is a DEVICE address
         getattr(L, "pdwt_bandbatch_stats_" + sfx).argtypes = [vp, C.POINTER(sz), ci, ci, C.POINTER(C.c_ubyte), C.POINTER(BandStats)]
         getattr(L, "pdwt_bandbatch_thresh_" + sfx).argtypes = [ci, vp, C.POINTER(sz), P, ci, ci]
+        # 2-D wavelet packets, one depth step: (parents, children, nr, nc, device node list or NULL, count, bank)
+        for d in ("wpt2d_forward_level", "wpt2d_inverse_level"):
+            getattr(L, "pdwt_%s_%s" % (d, sfx)).argtypes = [vp, vp, ci, ci, vp, ci, C.POINTER(FT)]
+        getattr(L, "pdwt_wpt2d_node_cost_" + sfx).argtypes = [vp, sz, ci, ci, C.POINTER(C.c_double)]
     _hip = L
     return L
 
@@ -291,6 +301,36 @@ def host(dtype):
             getattr(L, pfx + "threshold_bands").argtypes = [vp, vp, ci]
             getattr(L, pfx + "denoise").restype = C.c_double
             getattr(L, pfx + "denoise").argtypes = [vp, ci, C.c_double, ci, vp]
+        # WaveletPackets (include/wpt.h, wpt.cpp)
+        pi = C.POINTER(ci)
+        L.pdwt_wpt_new.restype = vp
+        L.pdwt_wpt_new.argtypes = [vp, ci, ci, C.c_char_p, ci, ci]
+        for n in ("delete", "forward", "inverse", "state", "basis_size"):
+            getattr(L, "pdwt_wpt_" + n).argtypes = [vp]
+        L.pdwt_wpt_get_image.argtypes = [vp, vp]
+        L.pdwt_wpt_set_image.argtypes = [vp, vp, ci]
+        L.pdwt_wpt_info.argtypes = [vp, C.POINTER(InfoWPT)]
+        L.pdwt_wpt_node_shape.restype = C.c_longlong
+        L.pdwt_wpt_node_shape.argtypes = [vp, ci, pi, pi]
+        L.pdwt_wpt_path_index.argtypes = [C.c_char_p, pi]
+        L.pdwt_wpt_geometry.argtypes = [ci, ci, ci, ci, pi, pi]
+        L.pdwt_wpt_get_node.argtypes = [vp, vp, ci, ci]
+        L.pdwt_wpt_get_level.restype = C.c_longlong
+        L.pdwt_wpt_get_level.argtypes = [vp, vp, ci]
+        L.pdwt_wpt_set_node.argtypes = [vp, vp, ci, ci, ci]
+        L.pdwt_wpt_node_int_ptr.restype = C.c_ssize_t
+        L.pdwt_wpt_node_int_ptr.argtypes = [vp, ci, ci]
+        L.pdwt_wpt_node_costs.argtypes = [vp, ci, ci, C.POINTER(C.c_double)]
+        L.pdwt_wpt_best_basis.argtypes = [vp, ci]
+        L.pdwt_wpt_set_basis.argtypes = [vp, pi, pi, ci]
+        L.pdwt_wpt_get_basis.argtypes = [vp, pi, pi]
+        for n in ("soft_threshold", "hard_threshold"):
+            getattr(L, "pdwt_wpt_" + n).argtypes = [vp, ct, ci]
+        L.pdwt_wpt_norm1.restype = C.c_double
+        L.pdwt_wpt_norm1.argtypes = [vp]
+        L.pdwt_wpt_node_stats.argtypes = [vp, ci, C.POINTER(BandStats)]
+        L.pdwt_wpt_estimate_sigma.restype = C.c_double
+        L.pdwt_wpt_estimate_sigma.argtypes = [vp]
         _host[dt] = L
     return _host[dt]
 
