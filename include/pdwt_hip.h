@@ -480,6 +480,37 @@ int pdwt_wpt2d_inverse_level_f64(double* d_parent, const double* d_child, int nr
 int pdwt_wpt2d_node_cost_f32(const float* d_nodes, size_t node_elems, int nnodes, int kind, double* out);
 int pdwt_wpt2d_node_cost_f64(const double* d_nodes, size_t node_elems, int nnodes, int kind, double* out);
 
+/* ---------------------------------------------------------------------------------------------
+ * 2-D DWT with boundary modes (pdwt_amd/csrc/dwt_ext.hip; the class: include/wt_ext.h).  The only transform here that does not
+ * periodise: a line x of n samples is extended past its ends by the mode (PyWavelets' names and semantics),
+ *   0 zero       0
+ *   1 constant   x[0] to the left, x[n-1] to the right
+ *   2 symmetric  half-sample mirror, period 2n       ... x1 x0 | x0 x1 ...
+ *   3 reflect    whole-sample mirror, period 2n - 2  ... x2 x1 | x0 x1 ...   (n == 1: the constant)
+ *   4 periodic   x[j mod n]
+ * and a bank of even length F gives N = (n + F - 1) / 2 coefficients per band (the full convolution at the odd indices):
+ *   a[i] = sum_k L[k] xe[2i + 1 - k],  d[i] = sum_k H[k] xe[2i + 1 - k],            i = 0 .. N-1, k = 0 .. F-1
+ *   x[k] = sum_i a[i] IL[k + F - 2 - 2i] + d[i] IH[k + F - 2 - 2i]  over the i whose tap index lies in 0 .. F-1,  k = 0 .. n-1
+ * The inverse reads no sample outside 0 .. N-1: it needs no extension and does not depend on the mode.  In 2-D rows first, then
+ * columns; the four bands have the orientation of the drivers above (A = row low / column low, H = row low / column high,
+ * V = row high / column low, D = row high / column high), each ((nr + F - 1) / 2) x ((nc + F - 1) / 2), row-major.
+ *
+ * The level entries run ONE level in ONE launch.  forward reads the nr x nc image d_src and writes the four bands; inverse reads
+ * the four bands and writes the nr x nc image d_dst.  An even f->hlen of 2 .. 40 (Haar included: the bank's own taps), nr and nc
+ * >= hlen - 1, nr * nc < 2^31, at most 65535 rows of tiles (nr below about 2^21), mode 0 .. 4; anything else, or a NULL pointer, is
+ * PDWT_EINVAL and nothing is launched.  Buffers need only be aligned to their element type.  Asynchronous on the library stream.
+ *
+ * Geometry of `levels` levels (1 .. 32) of an Nr x Nc image, no device needed: the band table is [A_L, H1, V1, D1, ..., H_L, V_L, D_L]
+ * (level 1 the finest).  num_bands: 3 * levels + 1; band_shape: the elements of band num, its shape in band_Nr / band_Nc when given;
+ * PDWT_EINVAL for sizes a level entry refuses or a bad num.  (The level clamp is the class's: include/wt_ext.h.)
+ * ------------------------------------------------------------------------------------------- */
+int pdwt_num_bands_ext(int Nr, int Nc, int hlen, int levels);
+long long pdwt_ext_band_shape(int Nr, int Nc, int hlen, int levels, int num, int* band_Nr, int* band_Nc);
+int pdwt_ext2d_forward_level_f32(const float* d_src, float* d_a, float* d_h, float* d_v, float* d_d, int nr, int nc, int mode, const pdwt_filters_f32* f);
+int pdwt_ext2d_forward_level_f64(const double* d_src, double* d_a, double* d_h, double* d_v, double* d_d, int nr, int nc, int mode, const pdwt_filters_f64* f);
+int pdwt_ext2d_inverse_level_f32(float* d_dst, const float* d_a, const float* d_h, const float* d_v, const float* d_d, int nr, int nc, const pdwt_filters_f32* f);
+int pdwt_ext2d_inverse_level_f64(double* d_dst, const double* d_a, const double* d_h, const double* d_v, const double* d_d, int nr, int nc, const pdwt_filters_f64* f);
+
 #ifdef __cplusplus
 }
 #endif

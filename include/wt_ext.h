@@ -1,0 +1,86 @@
+/*
+ * wt_ext.h -- `BoundaryWavelets`: the multi-level 2-D DWT with signal-extension boundary modes (no reference counterpart: the reference
+ * and every other class here periodise).  Same build as wt.h: plain host C++, DTYPE = float (libpdwt.so) or double (-DDOUBLEPRECISION,
+ * libpdwtd.so), every device action a C-ABI call into libpdwt_hip.so (include/pdwt_hip.h "2-D DWT with boundary modes"; kernels:
+ * pdwt_amd/csrc/dwt_ext.hip).
+ *
+ * Modes (PyWavelets' names and semantics): 0 zero, 1 constant, 2 symmetric (PyWavelets' default), 3 reflect, 4 periodic.  The
+ * transform is pywt.wavedec2 of those modes: a level takes an nr x nc approximation to four bands of ((nr + hlen - 1) / 2) x
+ * ((nc + hlen - 1) / 2), so the bands of L levels hold MORE samples than the image.  inverse() needs no mode and trims like
+ * pywt.waverec2.  Haar runs the bank's own taps (1/sqrt 2), not the 0.5 butterfly of the periodised Haar levels.
+ * Bands.  [A_L, H1, V1, D1, ..., H_L, V_L, D_L], level 1 the finest, the orientation of Wavelets (H = row low / column high).
+ * Levels are clamped as in Wavelets to ilog2(min(Nr, Nc) / (hlen - 1)) (PyWavelets' dwt_max_level) and to 32 (97 bands, the limit of
+ * the band-list kernels); a clamp to 0 levels is W_CREATION_ERROR.  Nr * Nc < 2^31.
+ * Storage.  All bands in ONE device allocation at 256-byte offsets, and two buffers of the size of a level-1 band for the
+ * intermediate approximations: forward() leaves the image intact, inverse() leaves the bands intact.  Device memory of an instance:
+ * about 2.5 images plus the halo growth of the bands.
+ * State machine: the w_state rules of Wavelets.  After inverse() reading a band, the thresholds, norm1 and the statistics are refused
+ * until the next forward(); set_image gives W_INIT; set_coeff is allowed in every state but W_CREATION_ERROR and leaves it alone
+ * (coefficients written from outside may be inverted without a forward()).  The statistics, threshold_bands and denoise need the
+ * coefficients of a forward() (W_FORWARD / W_THRESHOLD).
+ */
+#ifndef WT_EXT_H
+#define WT_EXT_H
+
+#include "wt.h"
+
+#define BW_MAX_LEVELS 32
+#define BW_NUM_MODES 5
+
+struct w_info_bw {
+    int Nr, Nc;
+    int nlevels; /* after clamping */
+    int hlen;
+    int mode;
+};
+
+class BoundaryWavelets {
+  public:
+    DTYPE* d_image;   /* device: image / reconstruction */
+    DTYPE** d_coeffs; /* HOST table of 3L+1 device pointers into one allocation */
+    char wname[128];
+    w_info_bw winfos;
+    w_state state;
+
+    BoundaryWavelets(DTYPE* img, int Nr, int Nc, const char* wname, int levels, int mode, int memisonhost = 1);
+    ~BoundaryWavelets();
+
+    void forward();
+    void inverse();
+    int get_image(DTYPE* img);
+    void set_image(DTYPE* img, int mem_is_on_device = 0);
+
+    /* the levels an instance of this size gets (levels < 1 asks for 1; clamped to ilog2(min(Nr, Nc) / (hlen - 1)) and BW_MAX_LEVELS;
+     * 0 = too small or a bad size / bank length) and, in nr / nc when given, the shape of the approximation of level 0 (the image) ..
+     * that level: the bands of level l are nr[l] x nc[l].  Needs no device.  What the constructor uses. */
+    static int geometry(int Nr, int Nc, int hlen, int levels, int* nr, int* nc);
+    /* the mode number of a PyWavelets mode name, -1 for any other */
+    static int mode_index(const char* name);
+
+    int num_bands() const;                                /* 3L+1; 0 after W_CREATION_ERROR */
+    long long coeff_shape(int num, int* nr, int* nc) const; /* elements of band num, 0 for a bad index */
+    int get_coeff(DTYPE* coeff, int num);                 /* elements copied, 0 when refused */
+    void set_coeff(DTYPE* coeff, int num, int mem_is_on_device = 0);
+    intptr_t image_int_ptr();
+    intptr_t coeff_int_ptr(int num);
+
+    /* every detail band; the approximation only when do_thresh_appcoeffs.  One launch. */
+    void soft_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
+    void hard_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
+    double norm1(); /* sum |c| over all bands, in double; -1 when refused */
+
+    /* the additions of wt.h on these bands (finest diagonal band = D1, N of the universal threshold = Nr * Nc), same meaning */
+    int band_stats(int num, w_band_stats* out, int with_median = 1);
+    int all_band_stats(w_band_stats* out, int with_median = 0);
+    double estimate_sigma();
+    void threshold_bands(const DTYPE* betas, int kind = 0);
+    double denoise(int method, double sigma = -1.0, int kind = 0, DTYPE* betas_out = NULL);
+
+  private:
+    void* priv_; /* bank, device, geometry, the ping buffers */
+    void threshold(int op, DTYPE beta, int do_thresh_appcoeffs);
+    BoundaryWavelets(const BoundaryWavelets&);
+    BoundaryWavelets& operator=(const BoundaryWavelets&);
+};
+
+#endif

@@ -23,6 +23,11 @@ class InfoWPT(C.Structure):
     _fields_ = [("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int)]
 
 
+class InfoBW(C.Structure):
+    """== w_info_bw (include/wt_ext.h)."""
+    _fields_ = [("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int), ("mode", C.c_int)]
+
+
 class BandStats(C.Structure):
     """== pdwt_band_stats (include/pdwt_hip.h) == w_band_stats (include/wt.h)."""
     _fields_ = [("n", C.c_double), ("sum_abs", C.c_double), ("sum_sq", C.c_double), ("max_abs", C.c_double), ("median_abs", C.c_double)]
@@ -62,7 +67,7 @@ PLAIN_SYMBOLS = ["pdwt_device_count", "pdwt_set_device", "pdwt_get_device", "pdw
                  "pdwt_batch2d_create_f32", "pdwt_batch2d_forward_f32", "pdwt_batch2d_inverse_f32", "pdwt_batch2d_destroy",
                  "pdwt_batch2d_create_f64", "pdwt_batch2d_forward_f64", "pdwt_batch2d_inverse_f64", "pdwt_batch2d_destroy_f64",
                  "pdwt_sum_scratch_doubles", "pdwt_sum_scratch_read", "pdwt_num_bands3d", "pdwt_band_size3d", "pdwt_tmp_elems3d",
-                 "pdwt_num_bands_swt3d", "pdwt_band_size_swt3d", "pdwt_tmp_elems_swt3d"]
+                 "pdwt_num_bands_swt3d", "pdwt_band_size_swt3d", "pdwt_tmp_elems_swt3d", "pdwt_num_bands_ext", "pdwt_ext_band_shape"]
 TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coeffs_buffer", "copy_coeffs_buffer",
                   "soft_thresh", "soft_thresh_sum", "norm1", "norm1_as_double", "norm1_enqueue", "hard_thresh", "proj_linf", "shrink", "group_soft_thresh",
                   "norm2sq", "norm2sq_as_double", "add_coeffs", "circshift", "forward_nonseparable", "inverse_nonseparable",
@@ -70,7 +75,7 @@ TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coe
                   "create_coeffs_buffer3d", "free_coeffs_buffer3d", "forward3d_separable", "inverse3d_separable", "soft_thresh3d", "hard_thresh3d",
                   "norm1_3d", "create_coeffs_buffer_swt3d", "free_coeffs_buffer_swt3d", "forward3d_swt", "inverse3d_swt",
                   "soft_thresh_swt3d", "hard_thresh_swt3d", "norm1_swt3d", "bandlist_stats", "bandlist_thresh", "bandbatch_stats", "bandbatch_thresh",
-                  "wpt2d_forward_level", "wpt2d_inverse_level", "wpt2d_node_cost"] + DRIVERS + HAAR_DRIVERS)
+                  "wpt2d_forward_level", "wpt2d_inverse_level", "wpt2d_node_cost", "ext2d_forward_level", "ext2d_inverse_level"] + DRIVERS + HAAR_DRIVERS)
 
 _hip = None
 _host = {}
@@ -146,6 +151,9 @@ def hip():
     L.pdwt_band_size_swt3d.argtypes = [Info3D, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
     L.pdwt_tmp_elems_swt3d.restype = sz
     L.pdwt_tmp_elems_swt3d.argtypes = [Info3D]
+    L.pdwt_num_bands_ext.argtypes = [ci, ci, ci, ci]
+    L.pdwt_ext_band_shape.restype = C.c_longlong
+    L.pdwt_ext_band_shape.argtypes = [ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci)]
     for sfx, ct, FT in (("f32", C.c_float, Filters32), ("f64", C.c_double, Filters64)):
         P = C.POINTER(ct)
         PP = C.POINTER(P)
@@ -200,6 +208,9 @@ def hip():
         for d in ("wpt2d_forward_level", "wpt2d_inverse_level"):
             getattr(L, "pdwt_%s_%s" % (d, sfx)).argtypes = [vp, vp, ci, ci, vp, ci, C.POINTER(FT)]
         getattr(L, "pdwt_wpt2d_node_cost_" + sfx).argtypes = [vp, sz, ci, ci, C.POINTER(C.c_double)]
+        # 2-D DWT with boundary modes, one level: (image, A, H, V, D, nr, nc, [mode,] bank)
+        getattr(L, "pdwt_ext2d_forward_level_" + sfx).argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, C.POINTER(FT)]
+        getattr(L, "pdwt_ext2d_inverse_level_" + sfx).argtypes = [vp, vp, vp, vp, vp, ci, ci, C.POINTER(FT)]
     _hip = L
     return L
 
@@ -292,8 +303,8 @@ def host(dtype):
             getattr(L, pfx + "image_int_ptr").argtypes = [vp]
             getattr(L, pfx + "coeff_int_ptr").restype = C.c_ssize_t
             getattr(L, pfx + "coeff_int_ptr").argtypes = [vp, ci]
-        # band statistics and noise-adaptive thresholds: the same five handle functions on the three classes
-        for pfx in ("pdwt_wavelets_", "pdwt_wavelets3d_", "pdwt_swt3d_"):
+        # band statistics and noise-adaptive thresholds: the same five handle functions on the four classes
+        for pfx in ("pdwt_wavelets_", "pdwt_wavelets3d_", "pdwt_swt3d_", "pdwt_bw_"):
             getattr(L, pfx + "band_stats").argtypes = [vp, ci, C.POINTER(BandStats), ci]
             getattr(L, pfx + "all_band_stats").argtypes = [vp, C.POINTER(BandStats), ci]
             getattr(L, pfx + "estimate_sigma").restype = C.c_double
@@ -331,6 +342,28 @@ def host(dtype):
         L.pdwt_wpt_node_stats.argtypes = [vp, ci, C.POINTER(BandStats)]
         L.pdwt_wpt_estimate_sigma.restype = C.c_double
         L.pdwt_wpt_estimate_sigma.argtypes = [vp]
+        # BoundaryWavelets (include/wt_ext.h, wt_ext.cpp)
+        L.pdwt_bw_new.restype = vp
+        L.pdwt_bw_new.argtypes = [vp, ci, ci, C.c_char_p, ci, ci, ci]
+        for n in ("delete", "forward", "inverse", "state", "num_bands"):
+            getattr(L, "pdwt_bw_" + n).argtypes = [vp]
+        L.pdwt_bw_get_image.argtypes = [vp, vp]
+        L.pdwt_bw_set_image.argtypes = [vp, vp, ci]
+        L.pdwt_bw_info.argtypes = [vp, C.POINTER(InfoBW)]
+        L.pdwt_bw_geometry.argtypes = [ci, ci, ci, ci, pi, pi]
+        L.pdwt_bw_mode_index.argtypes = [C.c_char_p]
+        L.pdwt_bw_coeff_shape.restype = C.c_longlong
+        L.pdwt_bw_coeff_shape.argtypes = [vp, ci, pi, pi]
+        L.pdwt_bw_get_coeff.argtypes = [vp, vp, ci]
+        L.pdwt_bw_set_coeff.argtypes = [vp, vp, ci, ci]
+        L.pdwt_bw_image_int_ptr.restype = C.c_ssize_t
+        L.pdwt_bw_image_int_ptr.argtypes = [vp]
+        L.pdwt_bw_coeff_int_ptr.restype = C.c_ssize_t
+        L.pdwt_bw_coeff_int_ptr.argtypes = [vp, ci]
+        for n in ("soft_threshold", "hard_threshold"):
+            getattr(L, "pdwt_bw_" + n).argtypes = [vp, ct, ci]
+        L.pdwt_bw_norm1.restype = C.c_double
+        L.pdwt_bw_norm1.argtypes = [vp]
         _host[dt] = L
     return _host[dt]
 

@@ -1,0 +1,177 @@
+"""Python view of the C++ ``BoundaryWavelets`` class (include/wt_ext.h): the multi-level 2-D DWT with signal-extension boundary modes
+-- ``zero``, ``constant``, ``symmetric`` (the default, as in PyWavelets), ``reflect``, ``periodic`` -- instead of the periodisation of
+``Wavelets``.  The bands are those of ``pywt.wavedec2(img, wname, mode, levels)``, in the order of ``Wavelets``:
+``[A_L, H1, V1, D1, ..., H_L, V_L, D_L]`` (level 1 the finest), each level ``(n + hlen - 1) // 2`` per axis.
+"""
+import ctypes as C
+
+import numpy as np
+
+from . import _native as N
+from .wavelets import DeviceArray, W_CREATION_ERROR, W_INVERSE, _BandStatsAPI, _device_source, _sync_producer
+
+MODES = {"zero": 0, "constant": 1, "symmetric": 2, "reflect": 3, "periodic": 4}
+
+
+class BoundaryWavelets2D(_BandStatsAPI):
+    """BoundaryWavelets2D(img, wname, levels, mode="symmetric", dtype=None): ``img`` is a 2-D numpy array or a contiguous float32 /
+    float64 device tensor (copied device to device, as ``Wavelets`` does).  Same state machine as ``Wavelets``; ``forward()`` leaves
+    the image intact and ``inverse()`` leaves the bands intact.  Levels are clamped to ilog2(min(Nr, Nc) / (hlen - 1)); an image too
+    small for one level, an unknown wavelet or an unknown mode number gives state W_CREATION_ERROR (an unknown mode NAME is a
+    ``ValueError`` here)."""
+
+    _hpfx = "pdwt_bw_"
+
+    def __init__(self, img, wname, levels, mode="symmetric", dtype=None):
+        N.require_gpu()
+        if isinstance(mode, str):
+            if mode not in MODES:
+                raise ValueError("mode must be one of %s" % ", ".join(MODES))
+            mode = MODES[mode]
+        dev = _device_source(img)
+        if dev is not None:
+            ptr, shape, dt = dev
+            if dtype is not None and np.dtype(dtype) != dt:
+                raise TypeError("dtype does not match the device tensor")
+            _sync_producer()
+            src, on_host, keep = C.c_void_p(ptr), 0, None
+        else:
+            img = np.asarray(img)
+            dt = np.dtype(dtype or (img.dtype if img.dtype in (np.float32, np.float64) else np.float32))
+            keep = np.ascontiguousarray(img, dtype=dt)
+            shape, src, on_host = keep.shape, keep.ctypes.data_as(C.c_void_p), 1
+        if len(shape) != 2:
+            raise ValueError("BoundaryWavelets2D needs a 2-D image (Nr, Nc)")
+        self.dtype, self.shape, self.wname = np.dtype(dt), tuple(int(v) for v in shape), wname
+        self._L = N.host(self.dtype)
+        self._ct = C.c_float if self.dtype == np.float32 else C.c_double
+        self._h = self._L.pdwt_bw_new(src, self.shape[0], self.shape[1], wname.encode(), int(levels), int(mode), on_host)
+        del keep
+        if not self._h:
+            raise MemoryError("BoundaryWavelets2D allocation failed")
+
+    def close(self):
+        if getattr(self, "_h", None):
+            self._L.pdwt_bw_delete(self._h)
+        self._h = None
+
+    __del__ = close
+
+    # -- introspection ---------------------------------------------------------------------
+    @property
+    def info(self):
+        i = N.InfoBW()
+        self._L.pdwt_bw_info(self._h, C.byref(i))
+        return i
+
+    @property
+    def levels(self):
+        return self.info.nlevels
+
+    @property
+    def mode(self):
+        """The name of the boundary mode (the number as given if it is not one of the five)."""
+        m = self.info.mode
+        return {v: k for k, v in MODES.items()}.get(m, m)
+
+    @property
+    def state(self):
+        return self._L.pdwt_bw_state(self._h)
+
+    @property
+    def nbands(self):
+        return self._L.pdwt_bw_num_bands(self._h)
+
+    def coeff_shape(self, num):
+        r, c = C.c_int(), C.c_int()
+        if self._L.pdwt_bw_coeff_shape(self._h, int(num), C.byref(r), C.byref(c)) <= 0:
+            raise IndexError(num)
+        return r.value, c.value
+
+    band_shape = coeff_shape
+
+    def _need_coeffs(self, what):
+        if self.state in (W_INVERSE, W_CREATION_ERROR):
+            raise RuntimeError("%s refused (state=%d): the coefficients are not valid" % (what, self.state))
+
+    # -- transforms ------------------------------------------------------------------------
+    def forward(self):
+        self._L.pdwt_bw_forward(self._h)
+
+    def inverse(self):
+        self._L.pdwt_bw_inverse(self._h)
+
+    # -- data in and out -------------------------------------------------------------------
+    def get_image(self):
+        out = np.empty(self.shape, dtype=self.dtype)
+        if self._L.pdwt_bw_get_image(self._h, out.ctypes.data_as(C.c_void_p)) != out.size:
+            raise RuntimeError("get_image failed (state=%d)" % self.state)
+        return out
+
+    def _upload(self, fn, arr, n, *args):
+        dev = _device_source(arr)
+        if dev is not None:
+            if dev[2] != self.dtype or int(np.prod(dev[1])) != n:
+                raise ValueError("device array of the wrong dtype or size")
+            _sync_producer()
+            return fn(self._h, C.c_void_p(dev[0]), *args, 1)
+        a = np.ascontiguousarray(arr, dtype=self.dtype)
+        if a.size != n:
+            raise ValueError("array of the wrong size")
+        return fn(self._h, a.ctypes.data_as(C.c_void_p), *args, 0)
+
+    def set_image(self, img):
+        if self.state == W_CREATION_ERROR:
+            raise RuntimeError("set_image refused (state=%d)" % self.state)
+        self._upload(self._L.pdwt_bw_set_image, img, self.shape[0] * self.shape[1])
+
+    def get_coeff(self, num):
+        self._need_coeffs("get_coeff")
+        out = np.empty(self.coeff_shape(num), dtype=self.dtype)
+        if self._L.pdwt_bw_get_coeff(self._h, out.ctypes.data_as(C.c_void_p), int(num)) != out.size:
+            raise RuntimeError("get_coeff(%d) failed (state=%d)" % (num, self.state))
+        return out
+
+    def set_coeff(self, arr, num):
+        """Overwrite one band (numpy array or device tensor).  Allowed in every state but W_CREATION_ERROR; the state stays."""
+        r, c = self.coeff_shape(num)
+        self._upload(self._L.pdwt_bw_set_coeff, arr, r * c, int(num))
+
+    @property
+    def coeffs(self):
+        return [self.get_coeff(k) for k in range(self.nbands)]
+
+    def image_int_ptr(self):
+        return self._L.pdwt_bw_image_int_ptr(self._h)
+
+    def coeff_int_ptr(self, num):
+        self.coeff_shape(num)
+        return self._L.pdwt_bw_coeff_int_ptr(self._h, int(num))
+
+    def image_view(self):
+        """The image as a zero-copy DeviceArray (call ``sync()`` before a consumer on another stream reads it)."""
+        return DeviceArray(self, self.image_int_ptr(), self.shape, self.dtype)
+
+    def coeff_view(self, num):
+        """Band ``num`` as a zero-copy DeviceArray."""
+        return DeviceArray(self, self.coeff_int_ptr(num), self.coeff_shape(num), self.dtype)
+
+    def sync(self):
+        return N.hip().pdwt_sync()
+
+    # -- thresholds and norms ----------------------------------------------------------------
+    def soft_threshold(self, beta, do_thresh_appcoeffs=0):
+        """In place on every detail band; the approximation only when ``do_thresh_appcoeffs``."""
+        self._need_coeffs("soft_threshold")
+        self._L.pdwt_bw_soft_threshold(self._h, self._ct(beta), int(do_thresh_appcoeffs))
+
+    def hard_threshold(self, beta, do_thresh_appcoeffs=0):
+        self._need_coeffs("hard_threshold")
+        self._L.pdwt_bw_hard_threshold(self._h, self._ct(beta), int(do_thresh_appcoeffs))
+
+    def norm1(self):
+        """Sum of |c| over all bands, in double."""
+        v = float(self._L.pdwt_bw_norm1(self._h))
+        if v < 0:
+            raise RuntimeError("norm1 refused (state=%d): the coefficients are not valid" % self.state)
+        return v
