@@ -511,6 +511,43 @@ int pdwt_ext2d_forward_level_f64(const double* d_src, double* d_a, double* d_h, 
 int pdwt_ext2d_inverse_level_f32(float* d_dst, const float* d_a, const float* d_h, const float* d_v, const float* d_d, int nr, int nc, const pdwt_filters_f32* f);
 int pdwt_ext2d_inverse_level_f64(double* d_dst, const double* d_a, const double* d_h, const double* d_v, const double* d_d, int nr, int nc, const pdwt_filters_f64* f);
 
+/* ---------------------------------------------------------------------------------------------
+ * Batched 1-D DWT with boundary modes (pdwt_amd/csrc/dwt_ext1d.hip; the class: BoundaryWavelets1D, include/wt_ext.h): the
+ * mathematics of the section above along the LAST axis only.  An nr x nc batch is nr independent lines of nc samples
+ * (pywt.wavedec(x, w, mode, level, axis=-1)); one level gives N = (nc + F - 1) / 2 coefficients per band and row, the modes are the
+ * numbers 0 .. 4 above, the inverse has no mode and trims like pywt.waverec.
+ * Band table of `levels` levels (1 .. 32): [A_L, D_1, ..., D_L], level 1 the finest, band l row-major nr x N_l -- the order of
+ * Wavelets with ndim = 1.  num_bands: levels + 1; band_len: the coefficients per row of band num; both need no device and return
+ * PDWT_EINVAL for what the entries refuse.
+ *
+ * Every entry takes an even f->hlen of 2 .. 40 (Haar: the bank's own taps), nr >= 1, nc >= hlen - 1 (7 samples of db4), nr * nc
+ * < 2^31 and a mode 0 .. 4; anything else, or a NULL pointer, is PDWT_EINVAL and nothing is launched.  Rows are not limited by a grid
+ * dimension.  Buffers need only be aligned to their element type.  Asynchronous on the library stream.
+ *
+ * The level entries run ONE level in one launch of the per-level kernels: forward reads d_src (nr x nc) and writes d_a and d_d
+ * (nr x N each); inverse reads them and writes d_dst (nr x nc).
+ * The whole-transform entries take d_coeffs, a HOST table of levels + 1 device pointers in the band order above.  When a row fits
+ * the LDS of a workgroup (pdwt_ext1d_fused: 1 / 0; float32 rows up to about 27 000 samples, float64 about 13 600) all levels run in
+ * ONE launch that reads the batch once and writes every band once, and d_tmp is not used (may be NULL).  Otherwise they loop the level
+ * kernels, keeping the intermediate approximations in d_tmp, which must hold pdwt_ext1d_tmp_elems elements (2 * nr * N_1; 0 for one
+ * level).  They return PDWT_EXT1D_FUSED or PDWT_EXT1D_LEVELS to tell which path ran, or a negative error.  Both paths give the same
+ * bits.  forward leaves d_src intact, inverse leaves the bands intact.
+ * ------------------------------------------------------------------------------------------- */
+#define PDWT_EXT1D_LEVELS 0 /* the per-level kernels ran */
+#define PDWT_EXT1D_FUSED 1  /* one launch ran all levels */
+int pdwt_num_bands_ext1d(int Nc, int hlen, int levels);
+long long pdwt_ext1d_band_len(int Nc, int hlen, int levels, int num);
+int pdwt_ext1d_fused(int Nc, int hlen, int levels, int elem_size);                      /* elem_size 4 or 8 */
+long long pdwt_ext1d_tmp_elems(int Nr, int Nc, int hlen, int levels, int elem_size);
+int pdwt_ext1d_forward_level_f32(const float* d_src, float* d_a, float* d_d, int nr, int nc, int mode, const pdwt_filters_f32* f);
+int pdwt_ext1d_forward_level_f64(const double* d_src, double* d_a, double* d_d, int nr, int nc, int mode, const pdwt_filters_f64* f);
+int pdwt_ext1d_inverse_level_f32(float* d_dst, const float* d_a, const float* d_d, int nr, int nc, const pdwt_filters_f32* f);
+int pdwt_ext1d_inverse_level_f64(double* d_dst, const double* d_a, const double* d_d, int nr, int nc, const pdwt_filters_f64* f);
+int pdwt_ext1d_forward_f32(const float* d_src, float* const* d_coeffs, int nr, int nc, int levels, int mode, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext1d_forward_f64(const double* d_src, double* const* d_coeffs, int nr, int nc, int levels, int mode, const pdwt_filters_f64* f, double* d_tmp);
+int pdwt_ext1d_inverse_f32(float* d_dst, float* const* d_coeffs, int nr, int nc, int levels, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext1d_inverse_f64(double* d_dst, double* const* d_coeffs, int nr, int nc, int levels, const pdwt_filters_f64* f, double* d_tmp);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,6 +3,7 @@
  * and every other class here periodise).  Same build as wt.h: plain host C++, DTYPE = float (libpdwt.so) or double (-DDOUBLEPRECISION,
  * libpdwtd.so), every device action a C-ABI call into libpdwt_hip.so (include/pdwt_hip.h "2-D DWT with boundary modes"; kernels:
  * pdwt_amd/csrc/dwt_ext.hip).
+ * `BoundaryWavelets1D`, further down, is the same transform along the last axis of a batch of rows.
  *
  * Modes (PyWavelets' names and semantics): 0 zero, 1 constant, 2 symmetric (PyWavelets' default), 3 reflect, 4 periodic.  The
  * transform is pywt.wavedec2 of those modes: a level takes an nr x nc approximation to four bands of ((nr + hlen - 1) / 2) x
@@ -81,6 +82,62 @@ class BoundaryWavelets {
     void threshold(int op, DTYPE beta, int do_thresh_appcoeffs);
     BoundaryWavelets(const BoundaryWavelets&);
     BoundaryWavelets& operator=(const BoundaryWavelets&);
+};
+
+/*
+ * `BoundaryWavelets1D`: the same along the LAST axis only, for a batch of Nr independent rows of Nc samples -- pywt.wavedec(x, wname,
+ * mode, levels, axis=-1) (include/pdwt_hip.h "Batched 1-D DWT with boundary modes"; kernels: pdwt_amd/csrc/dwt_ext1d.hip).  Member for
+ * member the class above, with these differences:
+ * Bands.  [A_L, D_1, ..., D_L], level 1 the finest, band l row-major Nr x N_l, N_l = (N_{l-1} + hlen - 1) / 2: the order of Wavelets
+ * with ndim = 1.  Levels are clamped to ilog2(Nc / (hlen - 1)) and to 32; a clamp to 0 levels is W_CREATION_ERROR.  Nr * Nc < 2^31.
+ * One launch.  When a row fits the LDS of a workgroup (fused() == 1) forward() and inverse() are ONE kernel launch each, whatever the
+ * number of levels: the batch is read once and every band written once.  Longer rows run one launch per level through a scratch
+ * buffer of two level-1 approximations, which only such an instance allocates.  Both paths give the same bits.
+ * Statistics.  The finest detail band is band 1 (all rows together); N of the universal threshold is Nc, the batched-1-D rule of wt.h.
+ */
+class BoundaryWavelets1D {
+  public:
+    DTYPE* d_image;   /* device: the batch / its reconstruction, Nr x Nc */
+    DTYPE** d_coeffs; /* HOST table of L+1 device pointers into one allocation */
+    char wname[128];
+    w_info_bw winfos;
+    w_state state;
+
+    BoundaryWavelets1D(DTYPE* img, int Nr, int Nc, const char* wname, int levels, int mode, int memisonhost = 1);
+    ~BoundaryWavelets1D();
+
+    void forward();
+    void inverse();
+    int get_image(DTYPE* img);
+    void set_image(DTYPE* img, int mem_is_on_device = 0);
+
+    /* the levels a row of Nc samples gets (levels < 1 asks for 1; clamped to ilog2(Nc / (hlen - 1)) and BW_MAX_LEVELS; 0 = too short or
+     * a bad size / bank length) and, in n when given, the samples per row of level 0 (the batch) .. that level.  Needs no device. */
+    static int geometry(int Nc, int hlen, int levels, int* n);
+
+    int num_bands() const;                                /* L+1; 0 after W_CREATION_ERROR */
+    long long coeff_shape(int num, int* nr, int* nc) const; /* elements of band num (Nr x N_l), 0 for a bad index */
+    int get_coeff(DTYPE* coeff, int num);
+    void set_coeff(DTYPE* coeff, int num, int mem_is_on_device = 0);
+    intptr_t image_int_ptr();
+    intptr_t coeff_int_ptr(int num);
+    int fused() const; /* 1: forward() and inverse() of this instance are one launch each; 0 after W_CREATION_ERROR */
+
+    void soft_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
+    void hard_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
+    double norm1();
+
+    int band_stats(int num, w_band_stats* out, int with_median = 1);
+    int all_band_stats(w_band_stats* out, int with_median = 0);
+    double estimate_sigma();
+    void threshold_bands(const DTYPE* betas, int kind = 0);
+    double denoise(int method, double sigma = -1.0, int kind = 0, DTYPE* betas_out = NULL);
+
+  private:
+    void* priv_; /* bank, device, geometry, the scratch of the per-level path */
+    void threshold(int op, DTYPE beta, int do_thresh_appcoeffs);
+    BoundaryWavelets1D(const BoundaryWavelets1D&);
+    BoundaryWavelets1D& operator=(const BoundaryWavelets1D&);
 };
 
 #endif

@@ -2,6 +2,9 @@
 -- ``zero``, ``constant``, ``symmetric`` (the default, as in PyWavelets), ``reflect``, ``periodic`` -- instead of the periodisation of
 ``Wavelets``.  The bands are those of ``pywt.wavedec2(img, wname, mode, levels)``, in the order of ``Wavelets``:
 ``[A_L, H1, V1, D1, ..., H_L, V_L, D_L]`` (level 1 the finest), each level ``(n + hlen - 1) // 2`` per axis.
+
+``BoundaryWavelets1D`` (C++ ``BoundaryWavelets1D``) is the same along the last axis of a batch of rows: ``pywt.wavedec(x, wname, mode,
+levels, axis=-1)``, bands ``[A_L, D_1, ..., D_L]``, all levels in one kernel launch when a row fits the LDS of a workgroup.
 """
 import ctypes as C
 
@@ -40,19 +43,24 @@ class BoundaryWavelets2D(_BandStatsAPI):
             dt = np.dtype(dtype or (img.dtype if img.dtype in (np.float32, np.float64) else np.float32))
             keep = np.ascontiguousarray(img, dtype=dt)
             shape, src, on_host = keep.shape, keep.ctypes.data_as(C.c_void_p), 1
-        if len(shape) != 2:
-            raise ValueError("BoundaryWavelets2D needs a 2-D image (Nr, Nc)")
+        shape = self._shape2(tuple(int(v) for v in shape))
         self.dtype, self.shape, self.wname = np.dtype(dt), tuple(int(v) for v in shape), wname
         self._L = N.host(self.dtype)
         self._ct = C.c_float if self.dtype == np.float32 else C.c_double
-        self._h = self._L.pdwt_bw_new(src, self.shape[0], self.shape[1], wname.encode(), int(levels), int(mode), on_host)
+        self._h = self._bs("new")(src, self.shape[0], self.shape[1], wname.encode(), int(levels), int(mode), on_host)
         del keep
         if not self._h:
-            raise MemoryError("BoundaryWavelets2D allocation failed")
+            raise MemoryError("%s allocation failed" % type(self).__name__)
+
+    @staticmethod
+    def _shape2(shape):
+        if len(shape) != 2:
+            raise ValueError("BoundaryWavelets2D needs a 2-D image (Nr, Nc)")
+        return shape
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.pdwt_bw_delete(self._h)
+            self._bs("delete")(self._h)
         self._h = None
 
     __del__ = close
@@ -61,7 +69,7 @@ class BoundaryWavelets2D(_BandStatsAPI):
     @property
     def info(self):
         i = N.InfoBW()
-        self._L.pdwt_bw_info(self._h, C.byref(i))
+        self._bs("info")(self._h, C.byref(i))
         return i
 
     @property
@@ -76,15 +84,15 @@ class BoundaryWavelets2D(_BandStatsAPI):
 
     @property
     def state(self):
-        return self._L.pdwt_bw_state(self._h)
+        return self._bs("state")(self._h)
 
     @property
     def nbands(self):
-        return self._L.pdwt_bw_num_bands(self._h)
+        return self._bs("num_bands")(self._h)
 
     def coeff_shape(self, num):
         r, c = C.c_int(), C.c_int()
-        if self._L.pdwt_bw_coeff_shape(self._h, int(num), C.byref(r), C.byref(c)) <= 0:
+        if self._bs("coeff_shape")(self._h, int(num), C.byref(r), C.byref(c)) <= 0:
             raise IndexError(num)
         return r.value, c.value
 
@@ -96,15 +104,15 @@ class BoundaryWavelets2D(_BandStatsAPI):
 
     # -- transforms ------------------------------------------------------------------------
     def forward(self):
-        self._L.pdwt_bw_forward(self._h)
+        self._bs("forward")(self._h)
 
     def inverse(self):
-        self._L.pdwt_bw_inverse(self._h)
+        self._bs("inverse")(self._h)
 
     # -- data in and out -------------------------------------------------------------------
     def get_image(self):
         out = np.empty(self.shape, dtype=self.dtype)
-        if self._L.pdwt_bw_get_image(self._h, out.ctypes.data_as(C.c_void_p)) != out.size:
+        if self._bs("get_image")(self._h, out.ctypes.data_as(C.c_void_p)) != out.size:
             raise RuntimeError("get_image failed (state=%d)" % self.state)
         return out
 
@@ -123,30 +131,30 @@ class BoundaryWavelets2D(_BandStatsAPI):
     def set_image(self, img):
         if self.state == W_CREATION_ERROR:
             raise RuntimeError("set_image refused (state=%d)" % self.state)
-        self._upload(self._L.pdwt_bw_set_image, img, self.shape[0] * self.shape[1])
+        self._upload(self._bs("set_image"), img, self.shape[0] * self.shape[1])
 
     def get_coeff(self, num):
         self._need_coeffs("get_coeff")
         out = np.empty(self.coeff_shape(num), dtype=self.dtype)
-        if self._L.pdwt_bw_get_coeff(self._h, out.ctypes.data_as(C.c_void_p), int(num)) != out.size:
+        if self._bs("get_coeff")(self._h, out.ctypes.data_as(C.c_void_p), int(num)) != out.size:
             raise RuntimeError("get_coeff(%d) failed (state=%d)" % (num, self.state))
         return out
 
     def set_coeff(self, arr, num):
         """Overwrite one band (numpy array or device tensor).  Allowed in every state but W_CREATION_ERROR; the state stays."""
         r, c = self.coeff_shape(num)
-        self._upload(self._L.pdwt_bw_set_coeff, arr, r * c, int(num))
+        self._upload(self._bs("set_coeff"), arr, r * c, int(num))
 
     @property
     def coeffs(self):
         return [self.get_coeff(k) for k in range(self.nbands)]
 
     def image_int_ptr(self):
-        return self._L.pdwt_bw_image_int_ptr(self._h)
+        return self._bs("image_int_ptr")(self._h)
 
     def coeff_int_ptr(self, num):
         self.coeff_shape(num)
-        return self._L.pdwt_bw_coeff_int_ptr(self._h, int(num))
+        return self._bs("coeff_int_ptr")(self._h, int(num))
 
     def image_view(self):
         """The image as a zero-copy DeviceArray (call ``sync()`` before a consumer on another stream reads it)."""
@@ -163,15 +171,40 @@ class BoundaryWavelets2D(_BandStatsAPI):
     def soft_threshold(self, beta, do_thresh_appcoeffs=0):
         """In place on every detail band; the approximation only when ``do_thresh_appcoeffs``."""
         self._need_coeffs("soft_threshold")
-        self._L.pdwt_bw_soft_threshold(self._h, self._ct(beta), int(do_thresh_appcoeffs))
+        self._bs("soft_threshold")(self._h, self._ct(beta), int(do_thresh_appcoeffs))
 
     def hard_threshold(self, beta, do_thresh_appcoeffs=0):
         self._need_coeffs("hard_threshold")
-        self._L.pdwt_bw_hard_threshold(self._h, self._ct(beta), int(do_thresh_appcoeffs))
+        self._bs("hard_threshold")(self._h, self._ct(beta), int(do_thresh_appcoeffs))
 
     def norm1(self):
         """Sum of |c| over all bands, in double."""
-        v = float(self._L.pdwt_bw_norm1(self._h))
+        v = float(self._bs("norm1")(self._h))
         if v < 0:
             raise RuntimeError("norm1 refused (state=%d): the coefficients are not valid" % self.state)
         return v
+
+
+class BoundaryWavelets1D(BoundaryWavelets2D):
+    """BoundaryWavelets1D(x, wname, levels, mode="symmetric", dtype=None): the batched 1-D DWT with the same boundary modes.  ``x`` is a
+    2-D ``(Nr, Nc)`` numpy array or contiguous device tensor of ``Nr`` independent rows (a 1-D array is one row); the transform runs
+    along the last axis only.  Bands ``[A_L, D_1, ..., D_L]`` (level 1 the finest), band ``l`` of shape ``(Nr, N_l)`` with
+    ``N_l = (N_{l-1} + hlen - 1) // 2``: the bands of ``pywt.wavedec(x, wname, mode, levels, axis=-1)`` in the order of
+    ``Wavelets(ndim=1)``.  Levels are clamped to ilog2(Nc / (hlen - 1)).  Same surface and state machine as ``BoundaryWavelets2D``;
+    the finest detail band of the statistics is band 1 (all rows together) and N of the universal threshold is Nc."""
+
+    _hpfx = "pdwt_bw1_"
+
+    @staticmethod
+    def _shape2(shape):
+        if len(shape) == 1:
+            return (1, shape[0])
+        if len(shape) != 2:
+            raise ValueError("BoundaryWavelets1D needs a batch of rows (Nr, Nc) or one row (Nc,)")
+        return shape
+
+    @property
+    def fused(self):
+        """True when ``forward()`` and ``inverse()`` of this instance are one kernel launch each (the rows fit the LDS of a workgroup);
+        False: one launch per level."""
+        return bool(self._bs("fused")(self._h))

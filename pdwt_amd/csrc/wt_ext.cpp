@@ -2,8 +2,11 @@
 // boundary modes"), and its flat C handle API (pdwt_bw_*, the shape of wpt.cpp).  Plain host C++ like wt.cpp, built into libpdwt.so
 // (float) and libpdwtd.so (-DDOUBLEPRECISION).  The geometry, the band table and the walk over the levels live here; the device only
 // ever sees one level.  Thresholds, norms and statistics go through the band-list entries (bandstats_host.hpp): no kernels of its own.
+// Below it `BoundaryWavelets1D`, the same along the last axis of a batch of rows, above the whole-transform entries of "Batched 1-D DWT
+// with boundary modes" (pdwt_bw1_*).
 #include <limits.h>
 #include <new>
+#include <stddef.h>
 #include <string.h>
 
 #include "../../include/pdwt_hip.h"
@@ -432,3 +435,376 @@ void pdwt_bw_threshold_bands(void* h, const DTYPE* betas, int kind) { BW(h)->thr
 double pdwt_bw_denoise(void* h, int method, double sigma, int kind, DTYPE* betas_out) { return BW(h)->denoise(method, sigma, kind, betas_out); }
 }
 #undef BW
+
+// =====================================================================================================================================
+// BoundaryWavelets1D: the same along the last axis of an Nr x Nc batch of rows (include/pdwt_hip.h "Batched 1-D DWT with boundary
+// modes").  The whole-transform entries choose between the one-launch kernels and the per-level loop; this class owns the band table and
+// the scratch of the loop, and shares the band-list code above.
+// =====================================================================================================================================
+namespace {
+struct bw1_priv {
+    bw_filters_t f;
+    int dev;        // the device current at construction; every method runs there
+    int n[kL + 1];  // [0] the samples of a row, [l] the coefficients per row of level l
+    int fused;      // the transforms of this instance are one launch each
+    DTYPE* d_bands; // the one allocation behind d_coeffs
+    DTYPE* d_tmp;   // the intermediate approximations of the per-level path; NULL when fused or for one level
+};
+static_assert(offsetof(bw1_priv, dev) == offsetof(bw_priv, dev), "DevScopeB reads the device of either class");
+inline bw1_priv* P1(void* p) { return (bw1_priv*)p; }
+void report1(const char* where, int rc) { printf("ERROR: BoundaryWavelets1D%s failed (code %d): %s\n", where, rc, pdwt_last_error_string()); }
+}  // namespace
+
+int BoundaryWavelets1D::geometry(int Nc, int hlen, int levels, int* n)
+{
+    if (Nc < 1 || hlen < 2 || hlen > PDWT_MAX_FILTER_WIDTH || (hlen & 1)) return 0;
+    if (levels < 1) levels = 1;
+    int wmaxlev = w_ilog2(Nc / (hlen - 1));  // the batched-1-D rule of Wavelets = PyWavelets' dwt_max_level
+    if (wmaxlev > kL) wmaxlev = kL;
+    if (levels > wmaxlev) levels = wmaxlev;
+    for (int l = 0; l <= levels; l++) {
+        if (n) n[l] = Nc;
+        Nc = (Nc + hlen - 1) >> 1;
+    }
+    return levels;
+}
+
+BoundaryWavelets1D::BoundaryWavelets1D(DTYPE* img, int Nr, int Nc, const char* wname_, int levels, int mode, int memisonhost)
+    : d_image(NULL), d_coeffs(NULL), state(W_INIT), priv_(NULL)
+{
+    winfos.Nr = Nr, winfos.Nc = Nc, winfos.nlevels = levels, winfos.hlen = 0, winfos.mode = mode;
+    strncpy(wname, wname_ ? wname_ : "", 127);
+    wname[127] = 0;
+    if (Nr < 1 || Nc < 1 || !wname_ || (unsigned long long)Nr * (unsigned long long)Nc >= (1ull << 31)) {
+        puts("ERROR: BoundaryWavelets1D(): invalid batch size or wavelet name");
+        state = W_CREATION_ERROR;
+        return;
+    }
+    if (mode < 0 || mode >= BW_NUM_MODES) {
+        printf("ERROR: BoundaryWavelets1D(): unknown boundary mode %d (0 zero, 1 constant, 2 symmetric, 3 reflect, 4 periodic)\n", mode);
+        state = W_CREATION_ERROR;
+        return;
+    }
+    if (levels < 1) {
+        puts("Warning: cannot initialize wavelet coefficients with nlevels < 1. Forcing nlevels = 1");
+        winfos.nlevels = 1;
+    }
+    bw1_priv* p = new (std::nothrow) bw1_priv();
+    if (!p) {
+        state = W_CREATION_ERROR;
+        return;
+    }
+    priv_ = p;
+    p->d_bands = p->d_tmp = NULL, p->fused = 0;
+    p->dev = pdwt_get_device();
+    const int hlen = SFX(pdwt_compute_filters_separable)(wname, 0, &p->f);
+    if (hlen <= 0) {
+        printf("ERROR: unknown wavelet name %s\n", wname);
+        state = W_CREATION_ERROR;
+        return;
+    }
+    p->f.hlen = hlen;
+    winfos.hlen = hlen;
+    const int wmaxlev = geometry(Nc, hlen, winfos.nlevels, p->n);
+    if (winfos.nlevels > wmaxlev) {
+        printf("Warning: required level (%d) is greater than the maximum possible level for %s (%d) on rows of %d samples.\n", winfos.nlevels, wname, wmaxlev, Nc);
+        printf("Forcing nlevels = %d\n", wmaxlev);
+        winfos.nlevels = wmaxlev;
+    }
+    if (winfos.nlevels < 1) {
+        printf("ERROR: rows of %d samples are too short for one level of %s\n", Nc, wname);
+        state = W_CREATION_ERROR;
+        return;
+    }
+    const int L = winfos.nlevels, nb = L + 1;
+    size_t off[kL + 1], total = 0;
+    for (int k = 0; k < nb; k++) {
+        off[k] = total;
+        total += ((size_t)Nr * p->n[k == 0 ? L : k] * sizeof(DTYPE) + 255) & ~(size_t)255;
+    }
+    const size_t n = (size_t)Nr * Nc;
+    const long long ntmp = pdwt_ext1d_tmp_elems(Nr, Nc, hlen, L, (int)sizeof(DTYPE));
+    p->fused = pdwt_ext1d_fused(Nc, hlen, L, (int)sizeof(DTYPE)) == 1;
+    d_image = (DTYPE*)pdwt_malloc(n * sizeof(DTYPE));
+    p->d_bands = (DTYPE*)pdwt_malloc(total);
+    d_coeffs = (DTYPE**)calloc((size_t)nb, sizeof(DTYPE*));
+    int rc = (d_image && p->d_bands && d_coeffs && ntmp >= 0) ? PDWT_OK : PDWT_ENOMEM;
+    if (rc == PDWT_OK && ntmp > 0) {
+        p->d_tmp = (DTYPE*)pdwt_malloc((size_t)ntmp * sizeof(DTYPE));
+        if (!p->d_tmp) rc = PDWT_ENOMEM;
+    }
+    if (rc == PDWT_OK) {
+        for (int k = 0; k < nb; k++) d_coeffs[k] = (DTYPE*)((char*)p->d_bands + off[k]);
+        rc = pdwt_memset(p->d_bands, 0, total);
+    }
+    if (rc == PDWT_OK) {
+        if (!img) rc = pdwt_memset(d_image, 0, n * sizeof(DTYPE));
+        else if (memisonhost) rc = pdwt_memcpy_h2d(d_image, img, n * sizeof(DTYPE));
+        else rc = pdwt_memcpy_d2d_foreign(d_image, img, n * sizeof(DTYPE));
+    }
+    if (rc != PDWT_OK) {
+        report1("(): allocation or upload", rc);
+        state = W_CREATION_ERROR;
+    }
+}
+
+BoundaryWavelets1D::~BoundaryWavelets1D()
+{
+    ON_MY_DEVICE_B();
+    if (d_image) pdwt_free(d_image);
+    free(d_coeffs);
+    if (priv_) {
+        bw1_priv* p = P1(priv_);
+        if (p->d_bands) pdwt_free(p->d_bands);
+        if (p->d_tmp) pdwt_free(p->d_tmp);
+        delete p;
+    }
+}
+
+void BoundaryWavelets1D::forward()
+{
+    ON_MY_DEVICE_B();
+    if (state == W_CREATION_ERROR) {
+        puts("Warning: forward transform not computed, as there was an error when creating the wavelets");
+        return;
+    }
+    bw1_priv* p = P1(priv_);
+    const int rc = SFX(pdwt_ext1d_forward)(d_image, d_coeffs, winfos.Nr, winfos.Nc, winfos.nlevels, winfos.mode, &p->f, p->d_tmp);
+    if (rc < 0) {
+        report1("::forward()", rc);
+        state = W_FORWARD_ERROR;
+        return;
+    }
+    state = W_FORWARD;
+}
+
+void BoundaryWavelets1D::inverse()
+{
+    ON_MY_DEVICE_B();
+    if (state == W_INVERSE) {
+        puts("Warning: W.inverse() has already been run. Inverse is available in W.get_image()");
+        return;
+    }
+    if (state == W_CREATION_ERROR || state == W_FORWARD_ERROR || state == W_THRESHOLD_ERROR) {
+        puts("Warning: inverse transform not computed, as there was an error in a previous stage");
+        return;
+    }
+    bw1_priv* p = P1(priv_);
+    const int rc = SFX(pdwt_ext1d_inverse)(d_image, d_coeffs, winfos.Nr, winfos.Nc, winfos.nlevels, &p->f, p->d_tmp);
+    if (rc < 0) {
+        report1("::inverse()", rc);
+        state = W_INVERSE_ERROR;
+        return;
+    }
+    state = W_INVERSE;
+}
+
+int BoundaryWavelets1D::get_image(DTYPE* res)
+{
+    ON_MY_DEVICE_B();
+    if (!d_image || !res || state == W_CREATION_ERROR) return 0;
+    const size_t n = (size_t)winfos.Nr * winfos.Nc;
+    if (pdwt_memcpy_d2h(res, d_image, n * sizeof(DTYPE)) != PDWT_OK) return 0;
+    return (int)n;
+}
+
+void BoundaryWavelets1D::set_image(DTYPE* img, int mem_is_on_device)
+{
+    ON_MY_DEVICE_B();
+    if (!d_image || !img || state == W_CREATION_ERROR) return;
+    const size_t nb = (size_t)winfos.Nr * winfos.Nc * sizeof(DTYPE);
+    const int rc = mem_is_on_device ? pdwt_memcpy_d2d_foreign(d_image, img, nb) : pdwt_memcpy_h2d(d_image, img, nb);
+    if (rc != PDWT_OK) report1("::set_image()", rc);
+    state = W_INIT;
+}
+
+int BoundaryWavelets1D::num_bands() const { return state == W_CREATION_ERROR ? 0 : winfos.nlevels + 1; }
+int BoundaryWavelets1D::fused() const { return state == W_CREATION_ERROR || !priv_ ? 0 : P1(priv_)->fused; }
+
+long long BoundaryWavelets1D::coeff_shape(int num, int* nr, int* nc) const
+{
+    if (state == W_CREATION_ERROR || num < 0 || num >= num_bands()) return 0;
+    const int len = P1(priv_)->n[num == 0 ? winfos.nlevels : num];
+    if (nr) *nr = winfos.Nr;
+    if (nc) *nc = len;
+    return (long long)winfos.Nr * len;
+}
+
+int BoundaryWavelets1D::get_coeff(DTYPE* coeff, int num)
+{
+    ON_MY_DEVICE_B();
+    if (state == W_INVERSE) {
+        puts("Warning: get_coeff(): inverse() has been performed; run forward() first.");
+        return 0;
+    }
+    const long long n = coeff_shape(num, NULL, NULL);
+    if (n <= 0 || !coeff) return 0;
+    if (pdwt_memcpy_d2h(coeff, d_coeffs[num], (size_t)n * sizeof(DTYPE)) != PDWT_OK) return 0;
+    return (int)n;
+}
+
+void BoundaryWavelets1D::set_coeff(DTYPE* coeff, int num, int mem_is_on_device)
+{
+    ON_MY_DEVICE_B();
+    const long long n = coeff_shape(num, NULL, NULL);
+    if (n <= 0 || !coeff) {
+        if (state != W_CREATION_ERROR) printf("ERROR: set_coeff(): invalid coefficient index %d\n", num);
+        return;
+    }
+    const size_t nb = (size_t)n * sizeof(DTYPE);
+    const int rc = mem_is_on_device ? pdwt_memcpy_d2d_foreign(d_coeffs[num], coeff, nb) : pdwt_memcpy_h2d(d_coeffs[num], coeff, nb);
+    if (rc != PDWT_OK) report1("::set_coeff()", rc);
+}
+
+intptr_t BoundaryWavelets1D::image_int_ptr() { return (intptr_t)d_image; }
+intptr_t BoundaryWavelets1D::coeff_int_ptr(int num) { return coeff_shape(num, NULL, NULL) > 0 ? (intptr_t)d_coeffs[num] : 0; }
+
+static pdwt_bl::BandList band_list(const BoundaryWavelets1D& W, bool need_forward)
+{
+    pdwt_bl::BandList bl;
+    bl.nb = 0;
+    if (W.state == W_CREATION_ERROR || W.state == W_INVERSE || !W.d_coeffs) return bl;
+    if (need_forward && !(W.state == W_FORWARD || W.state == W_THRESHOLD)) return bl;
+    const int nb = W.num_bands();
+    for (int k = 0; k < nb; k++) {
+        bl.ptr[k] = W.d_coeffs[k];
+        bl.n[k] = (size_t)W.coeff_shape(k, NULL, NULL);
+    }
+    bl.nb = nb;
+    bl.finest = 1;  // D1, all rows together
+    bl.samples = (double)W.winfos.Nc;  // the batched-1-D rule of wt.h: N of the universal threshold is the length of a signal
+    return bl;
+}
+
+void BoundaryWavelets1D::threshold(int op, DTYPE beta, int do_thresh_appcoeffs)
+{
+    ON_MY_DEVICE_B();
+    if (state == W_INVERSE) {
+        puts("Warning: BoundaryWavelets1D(): cannot threshold coefficients after W.inverse() (run forward() first)");
+        return;
+    }
+    const pdwt_bl::BandList bl = band_list(*this, false);
+    if (!bl.nb) return;
+    DTYPE betas[pdwt_bl::kMaxBands];
+    for (int k = 0; k < bl.nb; k++) betas[k] = beta;
+    if (!do_thresh_appcoeffs) betas[0] = (DTYPE)-1;
+    const int rc = pdwt_bl::threshold(bl, betas, op);
+    if (rc != PDWT_OK) {
+        report1(op ? "::hard_threshold()" : "::soft_threshold()", rc);
+        state = W_THRESHOLD_ERROR;
+    }
+}
+void BoundaryWavelets1D::soft_threshold(DTYPE beta, int do_thresh_appcoeffs) { threshold(0, beta, do_thresh_appcoeffs); }
+void BoundaryWavelets1D::hard_threshold(DTYPE beta, int do_thresh_appcoeffs) { threshold(1, beta, do_thresh_appcoeffs); }
+
+double BoundaryWavelets1D::norm1()
+{
+    ON_MY_DEVICE_B();
+    const pdwt_bl::BandList bl = band_list(*this, false);
+    if (!bl.nb) return -1.0;
+    w_band_stats s[pdwt_bl::kMaxBands];
+    const int rc = pdwt_bl::stats(bl, -1, s, 0);
+    if (rc != PDWT_OK) {
+        report1("::norm1()", rc);
+        return -1.0;
+    }
+    double sum = 0.0;
+    for (int k = 0; k < bl.nb; k++) sum += s[k].sum_abs;
+    return sum;
+}
+
+int BoundaryWavelets1D::band_stats(int num, w_band_stats* out, int with_median)
+{
+    ON_MY_DEVICE_B();
+    const pdwt_bl::BandList bl = band_list(*this, true);
+    if (!bl.nb || num < 0 || num >= bl.nb || !out) return PDWT_EINVAL;
+    const int rc = pdwt_bl::stats(bl, num, out, with_median);
+    if (rc != PDWT_OK) report1("::band_stats()", rc);
+    return rc;
+}
+
+int BoundaryWavelets1D::all_band_stats(w_band_stats* out, int with_median)
+{
+    ON_MY_DEVICE_B();
+    const pdwt_bl::BandList bl = band_list(*this, true);
+    if (!bl.nb || !out) return PDWT_EINVAL;
+    const int rc = pdwt_bl::stats(bl, -1, out, with_median);
+    if (rc != PDWT_OK) report1("::all_band_stats()", rc);
+    return rc;
+}
+
+double BoundaryWavelets1D::estimate_sigma()
+{
+    ON_MY_DEVICE_B();
+    const pdwt_bl::BandList bl = band_list(*this, true);
+    double sigma = -1.0;
+    if (!bl.nb) return -1.0;
+    const int rc = pdwt_bl::estimate_sigma(bl, &sigma);
+    if (rc != PDWT_OK) {
+        report1("::estimate_sigma()", rc);
+        return -1.0;
+    }
+    return sigma;
+}
+
+void BoundaryWavelets1D::threshold_bands(const DTYPE* betas, int kind)
+{
+    ON_MY_DEVICE_B();
+    const pdwt_bl::BandList bl = band_list(*this, true);
+    if (!bl.nb || !betas || (kind != 0 && kind != 1)) return;
+    const int rc = pdwt_bl::threshold(bl, betas, kind);
+    if (rc != PDWT_OK) {
+        report1("::threshold_bands()", rc);
+        state = W_THRESHOLD_ERROR;
+    }
+}
+
+double BoundaryWavelets1D::denoise(int method, double sigma, int kind, DTYPE* betas_out)
+{
+    ON_MY_DEVICE_B();
+    const pdwt_bl::BandList bl = band_list(*this, true);
+    if (!bl.nb || (method != 0 && method != 1) || (kind != 0 && kind != 1)) return -1.0;
+    DTYPE betas[pdwt_bl::kMaxBands];
+    const int rc = pdwt_bl::denoise(bl, method, kind, &sigma, betas);
+    if (rc != PDWT_OK) {
+        report1("::denoise()", rc);
+        state = W_THRESHOLD_ERROR;
+        return -1.0;
+    }
+    if (betas_out) memcpy(betas_out, betas, (size_t)bl.nb * sizeof(DTYPE));
+    return sigma;
+}
+
+// ---- flat C handle API (pdwt_amd/boundary.py), name for name with pdwt_bw_* --------------------------------------
+#define BW1(h) static_cast<BoundaryWavelets1D*>(h)
+extern "C" {
+void* pdwt_bw1_new(DTYPE* img, int Nr, int Nc, const char* wname, int levels, int mode, int memisonhost)
+{
+    return new (std::nothrow) BoundaryWavelets1D(img, Nr, Nc, wname, levels, mode, memisonhost);
+}
+void pdwt_bw1_delete(void* h) { delete BW1(h); }
+void pdwt_bw1_forward(void* h) { BW1(h)->forward(); }
+void pdwt_bw1_inverse(void* h) { BW1(h)->inverse(); }
+int pdwt_bw1_get_image(void* h, DTYPE* out) { return BW1(h)->get_image(out); }
+void pdwt_bw1_set_image(void* h, DTYPE* img, int mem_is_on_device) { BW1(h)->set_image(img, mem_is_on_device); }
+int pdwt_bw1_state(void* h) { return (int)BW1(h)->state; }
+void pdwt_bw1_info(void* h, w_info_bw* out) { *out = BW1(h)->winfos; }
+int pdwt_bw1_geometry(int Nc, int hlen, int levels, int* n) { return BoundaryWavelets1D::geometry(Nc, hlen, levels, n); }
+int pdwt_bw1_mode_index(const char* name) { return BoundaryWavelets::mode_index(name); }
+int pdwt_bw1_fused(void* h) { return BW1(h)->fused(); }
+int pdwt_bw1_num_bands(void* h) { return BW1(h)->num_bands(); }
+long long pdwt_bw1_coeff_shape(void* h, int num, int* nr, int* nc) { return BW1(h)->coeff_shape(num, nr, nc); }
+int pdwt_bw1_get_coeff(void* h, DTYPE* out, int num) { return BW1(h)->get_coeff(out, num); }
+void pdwt_bw1_set_coeff(void* h, DTYPE* in, int num, int mem_is_on_device) { BW1(h)->set_coeff(in, num, mem_is_on_device); }
+intptr_t pdwt_bw1_image_int_ptr(void* h) { return BW1(h)->image_int_ptr(); }
+intptr_t pdwt_bw1_coeff_int_ptr(void* h, int num) { return BW1(h)->coeff_int_ptr(num); }
+void pdwt_bw1_soft_threshold(void* h, DTYPE beta, int app) { BW1(h)->soft_threshold(beta, app); }
+void pdwt_bw1_hard_threshold(void* h, DTYPE beta, int app) { BW1(h)->hard_threshold(beta, app); }
+double pdwt_bw1_norm1(void* h) { return BW1(h)->norm1(); }
+int pdwt_bw1_band_stats(void* h, int num, w_band_stats* out, int with_median) { return BW1(h)->band_stats(num, out, with_median); }
+int pdwt_bw1_all_band_stats(void* h, w_band_stats* out, int with_median) { return BW1(h)->all_band_stats(out, with_median); }
+double pdwt_bw1_estimate_sigma(void* h) { return BW1(h)->estimate_sigma(); }
+void pdwt_bw1_threshold_bands(void* h, const DTYPE* betas, int kind) { BW1(h)->threshold_bands(betas, kind); }
+double pdwt_bw1_denoise(void* h, int method, double sigma, int kind, DTYPE* betas_out) { return BW1(h)->denoise(method, sigma, kind, betas_out); }
+}
+#undef BW1
