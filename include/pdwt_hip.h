@@ -221,7 +221,14 @@ long long pdwt_band_size(pdwt_info info, int num, int* band_Nr, int* band_Nc);
 /* test / tuning knobs (not part of the reference seam; names and meaning in INTEGRATION.md).  Each knob is
  * initialised ONCE from its PDWT_<NAME> environment variable and changed at run time only through
  * pdwt_debug_set; e.g. "force_twopass" = 1 makes the 2D DWT drivers use the two-pass (row kernel + column
- * kernel) form instead of the fused level kernels.  Unknown key: PDWT_EINVAL. */
+ * kernel) form instead of the fused level kernels.  Unknown key: PDWT_EINVAL.
+ * pdwt_debug_get also serves read-only launch counters (launches since the process started) for the tests
+ * that must know which of several kernels behind one timer id ran: stat_casc_spec_fwd / _inv, stat_lat_fwd /
+ * _inv, stat_inv_casc3, stat_inv_cascw, stat_inv_casc2, stat_fwd1d_fused, stat_inv1d_fused,
+ * stat_fwd1d_fused_ip, stat_inv1d_fused_ip, stat_ana_rows_tr, stat_syn_rows_tr, stat_ana_cols_ring,
+ * stat_syn_cols_ring, stat_swt_ana_rows_lds, stat_swt_syn_rows_lds, stat_swt_ana_cols_ring,
+ * stat_swt_syn_cols_ring, stat_swtf_fwd, stat_swtf_inv, stat_swtf_invp, stat_swtl2_fwd, stat_swtl2_inv,
+ * stat_swtd_fwd, stat_swtd_inv (csrc/common.hpp: StatId). */
 int pdwt_debug_set(const char* key, int value);
 int pdwt_debug_get(const char* key, int* value);
 

@@ -539,6 +539,7 @@ static int launch_ana(const T* t, T* lo, T* hi, const T* tB, T* loB, T* hiB, int
     const int strips = idiv_up(Ncw, 64 * CPL);
     const int RO = pick_chunk(div2(Nr), strips * nbr, HLEN);
     dim3 grid(idiv_up(strips, 4), idiv_up(div2(Nr), RO), nbr);
+    stat_hit(ST_ANA_COLS_RING);
     // taps beyond the SGPR budget: VGPR tap register + v_readlane (k_*_tr above)
     if constexpr (sizeof(T) == 8 && HLEN >= 20 && CPL == 1)
         hipLaunchKernelGGL((k_ana_cols_ring_tr<T, HLEN, CPL>), grid, dim3(256), 0, stream(), t, lo, hi, tB, loB, hiB, Nr, Ncw, RO, f);
@@ -554,6 +555,7 @@ static int launch_syn(const T* ca, const T* cd, T* out, const T* caB, const T* c
     const int strips = idiv_up(Nc, 64 * CPL);
     const int RQ = pick_chunk(Nri, strips * nbr, HLEN / 2);
     dim3 grid(idiv_up(strips, 4), idiv_up(Nri, RQ), nbr);
+    stat_hit(ST_SYN_COLS_RING);
     if constexpr (sizeof(T) == 8 && HLEN >= 20 && CPL == 1)
         hipLaunchKernelGGL((k_syn_cols_ring_tr<T, HLEN, CPL>), grid, dim3(256), 0, stream(), ca, cd, out, caB, cdB, outB, Nri, Nc, Nro, RQ, f);
     else
@@ -609,6 +611,7 @@ static int launch_swt_ana(const T* t, T* lo, T* hi, int Nr, int Nc, int fct, con
     int RO = pick_chunk(Nr, strips, HLEN);  // Nr rows in total = fct residue classes x M
     if (RO > M) RO = M;
     dim3 grid(idiv_up(strips, 4), fct * idiv_up(M, RO));
+    stat_hit(ST_SWT_ANA_COLS_RING);
     hipLaunchKernelGGL((k_swt_ana_cols_ring<T, HLEN, CPL>), grid, dim3(256), 0, stream(), t, lo, hi, Nr, Nc, fct, RO, f);
     PDWT_CHECK_LAUNCH();
     return PDWT_OK;
@@ -621,6 +624,7 @@ static int launch_swt_syn(const T* ca, const T* cd, T* out, int Nr, int Nc, int 
     int RO = pick_chunk(Nr, strips, HLEN);
     if (RO > M) RO = M;
     dim3 grid(idiv_up(strips, 4), fct * idiv_up(M, RO));
+    stat_hit(ST_SWT_SYN_COLS_RING);
     hipLaunchKernelGGL((k_swt_syn_cols_ring<T, HLEN, CPL>), grid, dim3(256), 0, stream(), ca, cd, out, Nr, Nc, fct, RO, f);
     PDWT_CHECK_LAUNCH();
     return PDWT_OK;

@@ -175,6 +175,34 @@ int knob(KnobId id);
 // stale registers there -> callers take the compiler-counted kernels.
 bool counted_waits_ok();
 void stat_casc_spec(int inverse);  // (test statistics: a wave-program kernel was launched)
+// Launch counters of the kernel families that share a KTimer id with the kernel they fall back to (read-only, for tests:
+// pdwt_debug_get("stat_<name>"), names in runtime.hip in this order; counted next to the launch, since the process started)
+enum StatId {
+    ST_INV_CASC3,  // dwt_casc_inv3.hip, two- and three-level forms
+    ST_INV_CASCW,  // dwt_casc_invw.hip
+    ST_INV_CASC2,  // inv2d_casc_f32, dwt_casc.hip
+    ST_FWD1D_FUSED,     // dwt1d_fused.hip: all levels of a row in one launch ...
+    ST_INV1D_FUSED,
+    ST_FWD1D_FUSED_IP,  // ... and its double-precision one-buffer kernels
+    ST_INV1D_FUSED_IP,
+    ST_ANA_ROWS_TR,  // rows_tr.hip
+    ST_SYN_ROWS_TR,
+    ST_ANA_COLS_RING,  // cols_ring.inc, decimated
+    ST_SYN_COLS_RING,
+    ST_SWT_ANA_ROWS_LDS,  // swt.hip: k_swt_rows_lds
+    ST_SWT_SYN_ROWS_LDS,
+    ST_SWT_ANA_COLS_RING,  // cols_ring.inc, stationary
+    ST_SWT_SYN_COLS_RING,
+    ST_SWTF_FWD,   // swt_fused.inc: fused SWT levels of up to 20 taps
+    ST_SWTF_INV,
+    ST_SWTF_INVP,  // ... the residue-major inverse
+    ST_SWTL2_FWD,  // swt_fused_l2.inc: 24 / 32 / 40 taps
+    ST_SWTL2_INV,
+    ST_SWTD_FWD,   // swt_fused_f64.inc
+    ST_SWTD_INV,
+    ST_COUNT
+};
+void stat_hit(StatId id);
 int knob_set(const char* name, int value);  // PDWT_OK / PDWT_EINVAL (unknown name)
 int knob_get(const char* name, int* value);
 

@@ -804,6 +804,7 @@ static int launch_fwd(const T* in, T** c, const pdwt_info& w, const Taps2<T>& f)
                 if (set_lds(k, lds1) != PDWT_OK) return PDWT_EHIP;
                 const int per_cu = std::max(1, std::min(8, (int)((160 * 1024) / (lds1 + 512))));
                 const int grid = w.Nr < 256 * per_cu ? w.Nr : 256 * per_cu;
+                stat_hit(ST_FWD1D_FUSED_IP);
                 KTimer kt(K_ANA_ROWS, true);
                 PDWT_LAUNCH_KT(kt, k, dim3(grid), dim3(256), lds1, in, b, w.Nr, f);
                 PDWT_CHECK_LAUNCH();
@@ -818,6 +819,7 @@ static int launch_fwd(const T* in, T** c, const pdwt_info& w, const Taps2<T>& f)
     // persistent workgroups: as many as fit the chip at once (256 CUs x LDS-limited residency), each walks rows
     const int per_cu = (int)((160 * 1024) / (lds + 512)) > 8 ? 8 : (int)((160 * 1024) / (lds + 512));
     const int grid = w.Nr < 256 * per_cu ? w.Nr : 256 * per_cu;
+    stat_hit(ST_FWD1D_FUSED);
     KTimer kt(K_ANA_ROWS, true);
     PDWT_LAUNCH_KT(kt, k, dim3(grid), dim3(256), lds, in, b, w.Nr, f);
     PDWT_CHECK_LAUNCH();
@@ -848,6 +850,7 @@ static int launch_inv(T* out, T** c, const pdwt_info& w, const Taps2<T>& f)
                 if (set_lds(k, lds2) != PDWT_OK) return PDWT_EHIP;
                 const int per_cu = std::max(1, std::min(8, (int)((160 * 1024) / (lds2 + 512))));
                 const int grid = w.Nr < 256 * per_cu ? w.Nr : 256 * per_cu;
+                stat_hit(ST_INV1D_FUSED_IP);
                 KTimer kt(K_SYN_ROWS, true);
                 PDWT_LAUNCH_KT(kt, k, dim3(grid), dim3(256), lds2, out, b, w.Nr, f);
                 PDWT_CHECK_LAUNCH();
@@ -861,6 +864,7 @@ static int launch_inv(T* out, T** c, const pdwt_info& w, const Taps2<T>& f)
         const int n = l == 0 ? b.n[w.nlevels] : b.n[l];
         pf = (n % NVh) == 0 && n / NVh <= 256 * inv_cap(l) && ((uintptr_t)b.p[l] & 15) == 0 && n >= NVh;
     }
+    stat_hit(ST_INV1D_FUSED);
     KTimer kt(K_SYN_ROWS, true);
     if (pf) {
         auto k = k_inv1d_fused_pf<T, HLEN>;

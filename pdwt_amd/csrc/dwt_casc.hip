@@ -1028,6 +1028,7 @@ static int launch_inv_casc(const CascInvBands& b, float* out, float* trash, int 
     if (cpx < 1) cpx = 1;
     const CascMap cm = {cpx, strips, 0};
     const dim3 grid((unsigned)(8 * idiv_up(cpx * strips, 4)));
+    stat_hit(ST_INV_CASC2);
     KTimer kt(K_INV2D_CASC, true);
     constexpr int H2 = HLEN / 2;
     // prefetch distance in steps: 1 measured best (28.2 us vs 29.5 @2, 31.5 @H2 for 4096^2 db4, 2048 waves)

@@ -819,6 +819,7 @@ static int launch_inv_casc3(const CascInvBands& b, const CascInv3B& b3, float* o
                        : (W == 4) ? lds_opt_in<k_inv2d_casc3<HLEN, 4, L3>>() : (W == 8) ? lds_opt_in<k_inv2d_casc3<HLEN, 8, L3>>() : (W == 12) ? lds_opt_in<k_inv2d_casc3<HLEN, 12, L3>>() : lds_opt_in<k_inv2d_casc3<HLEN, 16, L3>>();
         if (rc != PDWT_OK) return rc;
     }
+    stat_hit(ST_INV_CASC3);
     KTimer kt(K_INV2D_CASC, true);
     PDWT_LAUNCH_KT(kt, k, grid, dim3(64 * W), lds, b, b3, out, nr, nc, VL, trash, cm, f);
     PDWT_CHECK_LAUNCH();

@@ -488,6 +488,7 @@ static int launch_inv_cascw(const CascInvBands& b, const CascInv3* b3, float* ou
         if (rc != PDWT_OK) return rc;
     }
     const CascInv3 z3 = l3 ? *b3 : CascInv3{nullptr, nullptr, nullptr, nullptr};
+    stat_hit(ST_INV_CASCW);
     KTimer kt(K_INV2D_CASC, true);
     PDWT_LAUNCH_KT(kt, k, grid, dim3(64 * W), lds, b, z3, out, nr, nc, VL, trash, cm, f);
     PDWT_CHECK_LAUNCH();

@@ -240,6 +240,7 @@ static int launch_ana_tr(const double* in, double* lo, double* hi, int Nr, int N
     constexpr int NSLOT = (CIN + 1) / 2 + 4;
     const size_t lds = 4 * (size_t)NSLOT * 16;
     dim3 grid(idiv_up(div2(Nc), kRtTXO), idiv_up(Nr, 4));
+    stat_hit(ST_ANA_ROWS_TR);
     KTimer kt(K_ANA_ROWS);
     hipLaunchKernelGGL(k_ana_rows_tr<HLEN>, grid, dim3(256), lds, stream(), in, lo, hi, Nr, Nc, f);
     PDWT_CHECK_LAUNCH();
@@ -266,6 +267,7 @@ static int launch_syn_tr(const double* a, const double* d, double* out, int Nr, 
     constexpr int NSLOT = (CC + 1) / 2 + 2;
     const size_t lds = 4 * 2 * (size_t)NSLOT * 16;
     dim3 grid(idiv_up(Nci, kRtTXC), idiv_up(Nr, 4));
+    stat_hit(ST_SYN_ROWS_TR);
     KTimer kt(K_SYN_ROWS);
     hipLaunchKernelGGL(k_syn_rows_tr<HLEN>, grid, dim3(256), lds, stream(), a, d, out, Nr, Nci, Nco, f);
     PDWT_CHECK_LAUNCH();

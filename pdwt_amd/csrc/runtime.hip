@@ -113,6 +113,14 @@ void stat_casc_spec(int inverse) { (inverse ? g_stat_spec_inv : g_stat_spec_fwd)
 // ("stat_lat_fwd" / "stat_lat_inv": launches of the lattice level kernels of dwt_lat.hip)
 std::atomic<int> g_stat_lat_fwd{0}, g_stat_lat_inv{0};
 void stat_lat(int inverse) { (inverse ? g_stat_lat_inv : g_stat_lat_fwd).fetch_add(1, std::memory_order_relaxed); }
+// ("stat_<name>", StatId order of common.hpp: launches of the kernel families that share a timer id with their fallback)
+static const char* const g_stat_names[ST_COUNT] = {
+    "inv_casc3", "inv_cascw", "inv_casc2", "fwd1d_fused", "inv1d_fused", "fwd1d_fused_ip", "inv1d_fused_ip", "ana_rows_tr", "syn_rows_tr",
+    "ana_cols_ring", "syn_cols_ring", "swt_ana_rows_lds", "swt_syn_rows_lds", "swt_ana_cols_ring", "swt_syn_cols_ring",
+    "swtf_fwd", "swtf_inv", "swtf_invp", "swtl2_fwd", "swtl2_inv", "swtd_fwd", "swtd_inv",
+};
+static std::atomic<int> g_stat_hits[ST_COUNT];
+void stat_hit(StatId id) { g_stat_hits[id].fetch_add(1, std::memory_order_relaxed); }
 
 int knob_get(const char* name, int* value)
 {
@@ -125,6 +133,14 @@ int knob_get(const char* name, int* value)
     if (!strcmp(name, "stat_lat_fwd") || !strcmp(name, "stat_lat_inv")) {
         *value = (name[9] == 'f' ? g_stat_lat_fwd : g_stat_lat_inv).load(std::memory_order_relaxed);
         return PDWT_OK;
+    }
+    if (!strncmp(name, "stat_", 5)) {
+        for (int i = 0; i < ST_COUNT; i++) {
+            if (!strcmp(name + 5, g_stat_names[i])) {
+                *value = g_stat_hits[i].load(std::memory_order_relaxed);
+                return PDWT_OK;
+            }
+        }
     }
     for (int i = 0; i < KN_COUNT; i++) {
         if (!strcmp(name, g_knob_defs[i].name)) {

@@ -261,6 +261,7 @@ static int swt_rows_lds(const T* a, const T* d, T* o1, T* o2, int Nr, int Nc, in
     }
     const int per_cu = (int)((160 * 1024) / (lds + 256)) > 8 ? 8 : (int)((160 * 1024) / (lds + 256));
     const int grid = Nr < 256 * per_cu ? Nr : 256 * per_cu;
+    stat_hit(SYN ? ST_SWT_SYN_ROWS_LDS : ST_SWT_ANA_ROWS_LDS);
     KTimer kt(ktimer_id);
     hipLaunchKernelGGL(k, dim3(grid), dim3(256), lds, stream(), a, d, o1, o2, Nr, Nc, fct, HL, HR, f);
     PDWT_HIP_TRY(hipGetLastError());

@@ -599,6 +599,7 @@ static int launch_swt_fwd(const float* in, float* cA, float* cH, float* cV, floa
     }
     if (M > Mc) M = Mc;
     dim3 grid(tiles, fct * idiv_up(Mc, M), nimg);
+    stat_hit(ST_SWTF_FWD);
     KTimer kt(K_SWT_ANA_COLS, true);
     if (fct == 1) PDWT_LAUNCH_KT(kt, (k_swt_fwd_fused<HLEN, 1>), grid, dim3(256), lds, in, cA, cH, cV, cD, Nr, Nc, fct, M, f, knob(KN_SWTF_XCD), d_tbl);
     else if (fct == 2) PDWT_LAUNCH_KT(kt, (k_swt_fwd_fused<HLEN, 2>), grid, dim3(256), lds, in, cA, cH, cV, cD, Nr, Nc, fct, M, f, knob(KN_SWTF_XCD), d_tbl);
@@ -667,6 +668,7 @@ static int launch_swt_inv4(const float* cA, const float* cH, const float* cV, co
         if (rc <= 0) return rc;
     }
 #endif
+    stat_hit(ST_SWTF_INV);
     KTimer kt(K_SWT_SYN_COLS, true);
     if (fct == 1) PDWT_LAUNCH_KT(kt, (k_swt_inv_fused4<HLEN, 1>), grid, dim3(256), lds, cA, cH, cV, cD, out, Nr, Nc, fct, M, f, knob(KN_SWTF_XCD), knob(KN_SWTF_ALT), d_tbl);
     else if (fct == 2) PDWT_LAUNCH_KT(kt, (k_swt_inv_fused4<HLEN, 2>), grid, dim3(256), lds, cA, cH, cV, cD, out, Nr, Nc, fct, M, f, knob(KN_SWTF_XCD), knob(KN_SWTF_ALT), d_tbl);
@@ -720,6 +722,7 @@ static int launch_swt_invp(const float* cA, const float* cH, const float* cV, co
     if (ldsp > 64 * 1024) return 1;
     const int Mc = Nr / fct;
     dim3 grid(idiv_up(Nc, kSwtTile), fct * idiv_up(Mc, M), nimg);
+    if (fct == 4 || fct == 8 || fct == 16) stat_hit(ST_SWTF_INVP);
     KTimer kt(K_SWT_SYN_COLS, true);
     if (fct == 4) PDWT_LAUNCH_KT(kt, (k_swt_inv_fusedp<HLEN, 4>), grid, dim3(256), ldsp, cA, cH, cV, cD, out, Nr, Nc, M, f, knob(KN_SWTF_XCD), knob(KN_SWTF_ALT), d_tbl);
     else if (fct == 8) PDWT_LAUNCH_KT(kt, (k_swt_inv_fusedp<HLEN, 8>), grid, dim3(256), ldsp, cA, cH, cV, cD, out, Nr, Nc, M, f, knob(KN_SWTF_XCD), knob(KN_SWTF_ALT), d_tbl);

@@ -292,6 +292,7 @@ static int launch_swt_fwd_d(const double* in, double* cA, double* cH, double* cV
     const int Mc = Nr / fct, tiles = idiv_up(Nc, kSwtTileD);
     const int M = swtd_chunk_rows(Mc, fct, tiles, HLEN, 704, knob(KN_SWTF_M));
     dim3 grid(tiles, fct * idiv_up(Mc, M));
+    stat_hit(ST_SWTD_FWD);
     KTimer kt(K_SWT_ANA_COLS);
     if (fct == 1) hipLaunchKernelGGL((k_swt_fwd_fused_d<HLEN, 1>), grid, dim3(256), lds, stream(), in, cA, cH, cV, cD, Nr, Nc, fct, M, f, knob(KN_SWTF_XCD));
     else hipLaunchKernelGGL((k_swt_fwd_fused_d<HLEN, 0>), grid, dim3(256), lds, stream(), in, cA, cH, cV, cD, Nr, Nc, fct, M, f, knob(KN_SWTF_XCD));
@@ -326,6 +327,7 @@ static int launch_swt_inv_d(const double* cA, const double* cH, const double* cV
     const int Mc = Nr / fct, tiles = idiv_up(Nc, kSwtTileD);
     const int M = swtd_chunk_rows(Mc, fct, tiles, HLEN, 512, knob(KN_SWTF_MI));
     dim3 grid(tiles, fct * idiv_up(Mc, M));
+    stat_hit(ST_SWTD_INV);
     KTimer kt(K_SWT_SYN_COLS);
     if (fct == 1) hipLaunchKernelGGL((k_swt_inv_fused_d<HLEN, 1>), grid, dim3(256), lds, stream(), cA, cH, cV, cD, out, Nr, Nc, fct, M, f, knob(KN_SWTF_XCD));
     else hipLaunchKernelGGL((k_swt_inv_fused_d<HLEN, 0>), grid, dim3(256), lds, stream(), cA, cH, cV, cD, out, Nr, Nc, fct, M, f, knob(KN_SWTF_XCD));

@@ -346,6 +346,7 @@ static int launch_swt_fwd2(const float* in, float* cA, float* cH, float* cV, flo
     const int Mc = Nr / fct, tiles = idiv_up(Nc, kSwt2Tile);
     const int M = swt2_rows(Mc, fct, tiles, HLEN, knob(KN_SWTF_M), nimg);
     dim3 grid(tiles, fct * idiv_up(Mc, M), nimg);
+    stat_hit(ST_SWTL2_FWD);
     KTimer kt(K_SWT_ANA_COLS, true);
     if (fct == 1) PDWT_LAUNCH_KT(kt, (k_swt_fwd_fused2<HLEN, true>), grid, dim3(256), lds, in, cA, cH, cV, cD, Nr, Nc, fct, M, f, knob(KN_SWTF_XCD), d_tbl);
     else PDWT_LAUNCH_KT(kt, (k_swt_fwd_fused2<HLEN, false>), grid, dim3(256), lds, in, cA, cH, cV, cD, Nr, Nc, fct, M, f, knob(KN_SWTF_XCD), d_tbl);
@@ -413,6 +414,7 @@ static int launch_swt_inv2(const float* cA, const float* cH, const float* cV, co
     const int Mc = Nr / fct, tiles = idiv_up(Nc, kSwt2Tile);
     const int M = swt2_rows(Mc, fct, tiles, HLEN, knob(KN_SWTF_MI), nimg);
     dim3 grid(tiles, fct * idiv_up(Mc, M), nimg);
+    stat_hit(ST_SWTL2_INV);
     KTimer kt(K_SWT_SYN_COLS, true);
     if (fct == 1) return swt2_inv_fsel1(HLEN, kt, grid, lds, cA, cH, cV, cD, out, Nr, Nc, fct, M, f, knob(KN_SWTF_XCD), d_tbl);
     if (fct == 2) return swt2_inv_fsel2(HLEN, kt, grid, lds, cA, cH, cV, cD, out, Nr, Nc, fct, M, f, knob(KN_SWTF_XCD), d_tbl);
