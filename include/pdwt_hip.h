@@ -555,6 +555,41 @@ int pdwt_ext1d_forward_f64(const double* d_src, double* const* d_coeffs, int nr,
 int pdwt_ext1d_inverse_f32(float* d_dst, float* const* d_coeffs, int nr, int nc, int levels, const pdwt_filters_f32* f, float* d_tmp);
 int pdwt_ext1d_inverse_f64(double* d_dst, double* const* d_coeffs, int nr, int nc, int levels, const pdwt_filters_f64* f, double* d_tmp);
 
+/* ---------------------------------------------------------------------------------------------
+ * 3-D DWT with boundary modes (pdwt_amd/csrc/dwt_ext3d.hip; the class: BoundaryWavelets3D, include/wt_ext.h): the mathematics of
+ * "2-D DWT with boundary modes" along x (the last axis), then y, then z of an nz x nr x nc volume -- pywt.wavedecn(vol, w, mode,
+ * level).  One level gives eight bands of ((nz + F - 1) / 2) x ((nr + F - 1) / 2) x ((nc + F - 1) / 2), row-major; the modes are the
+ * numbers 0 .. 4 above; the inverse runs z, y, x, has no mode and trims like pywt.waverecn.
+ *
+ * The level entries run ONE level in TWO launches (x-y on every plane through d_tmp, then z; the inverse z, then x-y).  d_bands is a
+ * HOST array of 8 device pointers in the order aaa, aad, ada, add, daa, dad, dda, ddd (PyWavelets' dwtn keys; the first letter is
+ * the z axis, a = low pass).  forward reads d_src and writes the eight bands; inverse reads them and writes d_dst.  d_tmp holds the
+ * four x-y quadrants, 4 * nz * ((nr + F - 1) / 2) * ((nc + F - 1) / 2) elements (pdwt_ext3d_tmp_elems is enough); its contents
+ * afterwards are unspecified.  Band aaa may be the buffer of d_src / d_dst itself (it is written after the input has been read): the
+ * class keeps the approximation of a level in one scratch buffer that way.  forward leaves d_src intact otherwise, inverse leaves the
+ * bands intact.
+ * An even f->hlen of 2 .. 40 (Haar included: the bank's own taps), nz, nr and nc >= hlen - 1, nz <= 65535 (a grid dimension),
+ * nr * nc < 2^31 (lanes across a plane), at most 65535 rows of tiles (nr below about 2^21), mode 0 .. 4; anything else, or a NULL
+ * pointer (one of the eight included), is PDWT_EINVAL and nothing is launched.  Buffers need only be aligned to their element type.
+ * Asynchronous on the library stream.
+ *
+ * Geometry of `levels` levels (1 .. 13) of an Nz x Nr x Nc volume, no device needed: the band table is that of the periodised 3-D
+ * transform, [A_L, the 7 details of level L, ..., the 7 details of level 1] (detail k of level lev at 1 + 7 * (levels - lev) + k, in
+ * the order aad .. ddd).  num_bands: 7 * levels + 1; band_shape: the elements of band num, its shape in band_Nz / band_Nr / band_Nc
+ * when given; tmp_elems: the elements of scratch of an instance -- the four quadrants of level 1 plus one level-1 approximation, each
+ * padded to a multiple of 64 elements; tmp_approx_offset: where that approximation starts in the scratch, in elements (the quadrants
+ * of every level fit in front of it); all four PDWT_EINVAL for sizes a level entry refuses (band_shape also for a bad num).  (The
+ * level clamp is the class's: include/wt_ext.h.)
+ * ------------------------------------------------------------------------------------------- */
+int pdwt_num_bands_ext3d(int Nz, int Nr, int Nc, int hlen, int levels);
+long long pdwt_ext3d_band_shape(int Nz, int Nr, int Nc, int hlen, int levels, int num, int* band_Nz, int* band_Nr, int* band_Nc);
+long long pdwt_ext3d_tmp_elems(int Nz, int Nr, int Nc, int hlen);
+long long pdwt_ext3d_tmp_approx_offset(int Nz, int Nr, int Nc, int hlen);
+int pdwt_ext3d_forward_level_f32(const float* d_src, float* const* d_bands, int nz, int nr, int nc, int mode, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext3d_forward_level_f64(const double* d_src, double* const* d_bands, int nz, int nr, int nc, int mode, const pdwt_filters_f64* f, double* d_tmp);
+int pdwt_ext3d_inverse_level_f32(float* d_dst, float* const* d_bands, int nz, int nr, int nc, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext3d_inverse_level_f64(double* d_dst, double* const* d_bands, int nz, int nr, int nc, const pdwt_filters_f64* f, double* d_tmp);
+
 #ifdef __cplusplus
 }
 #endif

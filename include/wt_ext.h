@@ -3,7 +3,8 @@
  * and every other class here periodise).  Same build as wt.h: plain host C++, DTYPE = float (libpdwt.so) or double (-DDOUBLEPRECISION,
  * libpdwtd.so), every device action a C-ABI call into libpdwt_hip.so (include/pdwt_hip.h "2-D DWT with boundary modes"; kernels:
  * pdwt_amd/csrc/dwt_ext.hip).
- * `BoundaryWavelets1D`, further down, is the same transform along the last axis of a batch of rows.
+ * `BoundaryWavelets1D`, further down, is the same transform along the last axis of a batch of rows; `BoundaryWavelets3D`, below
+ * it, along the three axes of a volume.
  *
  * Modes (PyWavelets' names and semantics): 0 zero, 1 constant, 2 symmetric (PyWavelets' default), 3 reflect, 4 periodic.  The
  * transform is pywt.wavedec2 of those modes: a level takes an nr x nc approximation to four bands of ((nr + hlen - 1) / 2) x
@@ -138,6 +139,75 @@ class BoundaryWavelets1D {
     void threshold(int op, DTYPE beta, int do_thresh_appcoeffs);
     BoundaryWavelets1D(const BoundaryWavelets1D&);
     BoundaryWavelets1D& operator=(const BoundaryWavelets1D&);
+};
+
+/*
+ * `BoundaryWavelets3D`: the same along all three axes of an Nz x Nr x Nc volume -- pywt.wavedecn(vol, wname, mode, levels)
+ * (include/pdwt_hip.h "3-D DWT with boundary modes"; kernels: pdwt_amd/csrc/dwt_ext3d.hip).  One level applies the one-axis formula
+ * along x (the last axis), then y, then z, and takes an nz x nr x nc approximation to eight bands of ((nz + hlen - 1) / 2) x
+ * ((nr + hlen - 1) / 2) x ((nc + hlen - 1) / 2).  Member for member the first class above, with these differences:
+ * Bands.  The order of Wavelets3D (include/wt3d.h) and of pywt.wavedecn: [A_L, the 7 details of level L, ..., those of level 1];
+ * detail k of level lev (1 = finest) is band 1 + 7 * (L - lev) + k, k in the order aad, ada, add, daa, dad, dda, ddd (first letter =
+ * z axis).  Levels are clamped to ilog2(min(Nz, Nr, Nc) / (hlen - 1)) and to 13 (92 bands); a clamp to 0 levels is W_CREATION_ERROR.
+ * Nz <= 65535 and Nr * Nc < 2^31.
+ * Storage.  All bands in ONE zero-filled device allocation at 256-byte offsets, and one scratch buffer of four level-1 quadrants
+ * (Nz x N_r1 x N_c1 each) plus one level-1 approximation, through which the approximation of every level but the last goes: forward()
+ * leaves the volume intact, inverse() leaves the bands intact.  Two launches per level and direction.
+ * Statistics.  The finest diagonal band is ddd of level 1 (band 7L); N of the universal threshold is Nz * Nr * Nc.
+ */
+#define BW3_MAX_LEVELS 13
+
+struct w_info_bw3 {
+    int Nz, Nr, Nc;
+    int nlevels; /* after clamping */
+    int hlen;
+    int mode;
+};
+
+class BoundaryWavelets3D {
+  public:
+    DTYPE* d_image;   /* device: the volume / its reconstruction */
+    DTYPE** d_coeffs; /* HOST table of 7L+1 device pointers into one allocation */
+    char wname[128];
+    w_info_bw3 winfos;
+    w_state state;
+
+    BoundaryWavelets3D(DTYPE* vol, int Nz, int Nr, int Nc, const char* wname, int levels, int mode, int memisonhost = 1);
+    ~BoundaryWavelets3D();
+
+    void forward();
+    void inverse();
+    int get_image(DTYPE* vol);
+    void set_image(DTYPE* vol, int mem_is_on_device = 0);
+
+    /* the levels a volume of this size gets (levels < 1 asks for 1; clamped to ilog2(min(Nz, Nr, Nc) / (hlen - 1)) and
+     * BW3_MAX_LEVELS; 0 = too small or a bad size / bank length) and, in nz / nr / nc when given, the shape of the approximation of
+     * level 0 (the volume) .. that level: the bands of level l are nz[l] x nr[l] x nc[l].  Needs no device. */
+    static int geometry(int Nz, int Nr, int Nc, int hlen, int levels, int* nz, int* nr, int* nc);
+
+    int num_bands() const;                                           /* 7L+1; 0 after W_CREATION_ERROR */
+    long long coeff_shape(int num, int* nz, int* nr, int* nc) const; /* elements of band num, 0 for a bad index */
+    int get_coeff(DTYPE* coeff, int num);                            /* elements copied, 0 when refused */
+    void set_coeff(DTYPE* coeff, int num, int mem_is_on_device = 0);
+    intptr_t image_int_ptr();
+    intptr_t coeff_int_ptr(int num);
+
+    /* every detail band; the approximation only when do_thresh_appcoeffs.  One launch. */
+    void soft_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
+    void hard_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
+    double norm1(); /* sum |c| over all bands, in double; -1 when refused */
+
+    int band_stats(int num, w_band_stats* out, int with_median = 1);
+    int all_band_stats(w_band_stats* out, int with_median = 0);
+    double estimate_sigma();
+    void threshold_bands(const DTYPE* betas, int kind = 0);
+    double denoise(int method, double sigma = -1.0, int kind = 0, DTYPE* betas_out = NULL);
+
+  private:
+    void* priv_; /* bank, device, geometry, the band allocation, the scratch */
+    void threshold(int op, DTYPE beta, int do_thresh_appcoeffs);
+    BoundaryWavelets3D(const BoundaryWavelets3D&);
+    BoundaryWavelets3D& operator=(const BoundaryWavelets3D&);
 };
 
 #endif

@@ -28,6 +28,11 @@ class InfoBW(C.Structure):
     _fields_ = [("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int), ("mode", C.c_int)]
 
 
+class InfoBW3(C.Structure):
+    """== w_info_bw3 (include/wt_ext.h)."""
+    _fields_ = [("Nz", C.c_int), ("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int), ("mode", C.c_int)]
+
+
 class BandStats(C.Structure):
     """== pdwt_band_stats (include/pdwt_hip.h) == w_band_stats (include/wt.h)."""
     _fields_ = [("n", C.c_double), ("sum_abs", C.c_double), ("sum_sq", C.c_double), ("max_abs", C.c_double), ("median_abs", C.c_double)]
@@ -68,7 +73,8 @@ PLAIN_SYMBOLS = ["pdwt_device_count", "pdwt_set_device", "pdwt_get_device", "pdw
                  "pdwt_batch2d_create_f64", "pdwt_batch2d_forward_f64", "pdwt_batch2d_inverse_f64", "pdwt_batch2d_destroy_f64",
                  "pdwt_sum_scratch_doubles", "pdwt_sum_scratch_read", "pdwt_num_bands3d", "pdwt_band_size3d", "pdwt_tmp_elems3d",
                  "pdwt_num_bands_swt3d", "pdwt_band_size_swt3d", "pdwt_tmp_elems_swt3d", "pdwt_num_bands_ext", "pdwt_ext_band_shape",
-                 "pdwt_num_bands_ext1d", "pdwt_ext1d_band_len", "pdwt_ext1d_fused", "pdwt_ext1d_tmp_elems"]
+                 "pdwt_num_bands_ext1d", "pdwt_ext1d_band_len", "pdwt_ext1d_fused", "pdwt_ext1d_tmp_elems",
+                 "pdwt_num_bands_ext3d", "pdwt_ext3d_band_shape", "pdwt_ext3d_tmp_elems", "pdwt_ext3d_tmp_approx_offset"]
 TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coeffs_buffer", "copy_coeffs_buffer",
                   "soft_thresh", "soft_thresh_sum", "norm1", "norm1_as_double", "norm1_enqueue", "hard_thresh", "proj_linf", "shrink", "group_soft_thresh",
                   "norm2sq", "norm2sq_as_double", "add_coeffs", "circshift", "forward_nonseparable", "inverse_nonseparable",
@@ -77,7 +83,8 @@ TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coe
                   "norm1_3d", "create_coeffs_buffer_swt3d", "free_coeffs_buffer_swt3d", "forward3d_swt", "inverse3d_swt",
                   "soft_thresh_swt3d", "hard_thresh_swt3d", "norm1_swt3d", "bandlist_stats", "bandlist_thresh", "bandbatch_stats", "bandbatch_thresh",
                   "wpt2d_forward_level", "wpt2d_inverse_level", "wpt2d_node_cost", "ext2d_forward_level", "ext2d_inverse_level",
-                  "ext1d_forward_level", "ext1d_inverse_level", "ext1d_forward", "ext1d_inverse"] + DRIVERS + HAAR_DRIVERS)
+                  "ext1d_forward_level", "ext1d_inverse_level", "ext1d_forward", "ext1d_inverse",
+                  "ext3d_forward_level", "ext3d_inverse_level"] + DRIVERS + HAAR_DRIVERS)
 
 _hip = None
 _host = {}
@@ -219,6 +226,16 @@ def hip():
         getattr(L, "pdwt_ext1d_inverse_level_" + sfx).argtypes = [vp, vp, vp, ci, ci, C.POINTER(FT)]
         getattr(L, "pdwt_ext1d_forward_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, C.POINTER(FT), vp]
         getattr(L, "pdwt_ext1d_inverse_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, C.POINTER(FT), vp]
+        # volumes with boundary modes, one level: (volume, HOST table of the 8 band pointers aaa .. ddd, nz, nr, nc, [mode,] bank, scratch)
+        getattr(L, "pdwt_ext3d_forward_level_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, C.POINTER(FT), vp]
+        getattr(L, "pdwt_ext3d_inverse_level_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, C.POINTER(FT), vp]
+    L.pdwt_num_bands_ext3d.argtypes = [ci, ci, ci, ci, ci]
+    L.pdwt_ext3d_band_shape.restype = C.c_longlong
+    L.pdwt_ext3d_band_shape.argtypes = [ci, ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
+    L.pdwt_ext3d_tmp_elems.restype = C.c_longlong
+    L.pdwt_ext3d_tmp_elems.argtypes = [ci, ci, ci, ci]
+    L.pdwt_ext3d_tmp_approx_offset.restype = C.c_longlong
+    L.pdwt_ext3d_tmp_approx_offset.argtypes = [ci, ci, ci, ci]
     L.pdwt_num_bands_ext1d.argtypes = [ci, ci, ci]
     L.pdwt_ext1d_band_len.restype = C.c_longlong
     L.pdwt_ext1d_band_len.argtypes = [ci, ci, ci, ci]
@@ -318,7 +335,7 @@ def host(dtype):
             getattr(L, pfx + "coeff_int_ptr").restype = C.c_ssize_t
             getattr(L, pfx + "coeff_int_ptr").argtypes = [vp, ci]
         # band statistics and noise-adaptive thresholds: the same five handle functions on the four classes
-        for pfx in ("pdwt_wavelets_", "pdwt_wavelets3d_", "pdwt_swt3d_", "pdwt_bw_", "pdwt_bw1_"):
+        for pfx in ("pdwt_wavelets_", "pdwt_wavelets3d_", "pdwt_swt3d_", "pdwt_bw_", "pdwt_bw1_", "pdwt_bw3_"):
             getattr(L, pfx + "band_stats").argtypes = [vp, ci, C.POINTER(BandStats), ci]
             getattr(L, pfx + "all_band_stats").argtypes = [vp, C.POINTER(BandStats), ci]
             getattr(L, pfx + "estimate_sigma").restype = C.c_double
@@ -399,6 +416,27 @@ def host(dtype):
             getattr(L, "pdwt_bw1_" + n).argtypes = [vp, ct, ci]
         L.pdwt_bw1_norm1.restype = C.c_double
         L.pdwt_bw1_norm1.argtypes = [vp]
+        L.pdwt_bw3_new.restype = vp
+        L.pdwt_bw3_new.argtypes = [vp, ci, ci, ci, C.c_char_p, ci, ci, ci]
+        for n in ("delete", "forward", "inverse", "state", "num_bands"):
+            getattr(L, "pdwt_bw3_" + n).argtypes = [vp]
+        L.pdwt_bw3_get_image.argtypes = [vp, vp]
+        L.pdwt_bw3_set_image.argtypes = [vp, vp, ci]
+        L.pdwt_bw3_info.argtypes = [vp, C.POINTER(InfoBW3)]
+        L.pdwt_bw3_geometry.argtypes = [ci, ci, ci, ci, ci, pi, pi, pi]
+        L.pdwt_bw3_mode_index.argtypes = [C.c_char_p]
+        L.pdwt_bw3_coeff_shape.restype = C.c_longlong
+        L.pdwt_bw3_coeff_shape.argtypes = [vp, ci, pi, pi, pi]
+        L.pdwt_bw3_get_coeff.argtypes = [vp, vp, ci]
+        L.pdwt_bw3_set_coeff.argtypes = [vp, vp, ci, ci]
+        L.pdwt_bw3_image_int_ptr.restype = C.c_ssize_t
+        L.pdwt_bw3_image_int_ptr.argtypes = [vp]
+        L.pdwt_bw3_coeff_int_ptr.restype = C.c_ssize_t
+        L.pdwt_bw3_coeff_int_ptr.argtypes = [vp, ci]
+        for n in ("soft_threshold", "hard_threshold"):
+            getattr(L, "pdwt_bw3_" + n).argtypes = [vp, ct, ci]
+        L.pdwt_bw3_norm1.restype = C.c_double
+        L.pdwt_bw3_norm1.argtypes = [vp]
         _host[dt] = L
     return _host[dt]
 

@@ -5,6 +5,9 @@
 
 ``BoundaryWavelets1D`` (C++ ``BoundaryWavelets1D``) is the same along the last axis of a batch of rows: ``pywt.wavedec(x, wname, mode,
 levels, axis=-1)``, bands ``[A_L, D_1, ..., D_L]``, all levels in one kernel launch when a row fits the LDS of a workgroup.
+
+``BoundaryWavelets3D`` (C++ ``BoundaryWavelets3D``) is the same along the three axes of a volume: ``pywt.wavedecn(vol, wname, mode,
+levels)``, bands in the order of ``Wavelets3D``.
 """
 import ctypes as C
 
@@ -12,6 +15,7 @@ import numpy as np
 
 from . import _native as N
 from .wavelets import DeviceArray, W_CREATION_ERROR, W_INVERSE, _BandStatsAPI, _device_source, _sync_producer
+from .wavelets3d import BAND_KEYS
 
 MODES = {"zero": 0, "constant": 1, "symmetric": 2, "reflect": 3, "periodic": 4}
 
@@ -47,7 +51,7 @@ class BoundaryWavelets2D(_BandStatsAPI):
         self.dtype, self.shape, self.wname = np.dtype(dt), tuple(int(v) for v in shape), wname
         self._L = N.host(self.dtype)
         self._ct = C.c_float if self.dtype == np.float32 else C.c_double
-        self._h = self._bs("new")(src, self.shape[0], self.shape[1], wname.encode(), int(levels), int(mode), on_host)
+        self._h = self._bs("new")(src, *self.shape, wname.encode(), int(levels), int(mode), on_host)
         del keep
         if not self._h:
             raise MemoryError("%s allocation failed" % type(self).__name__)
@@ -66,9 +70,11 @@ class BoundaryWavelets2D(_BandStatsAPI):
     __del__ = close
 
     # -- introspection ---------------------------------------------------------------------
+    _info_t = N.InfoBW
+
     @property
     def info(self):
-        i = N.InfoBW()
+        i = self._info_t()
         self._bs("info")(self._h, C.byref(i))
         return i
 
@@ -131,7 +137,7 @@ class BoundaryWavelets2D(_BandStatsAPI):
     def set_image(self, img):
         if self.state == W_CREATION_ERROR:
             raise RuntimeError("set_image refused (state=%d)" % self.state)
-        self._upload(self._bs("set_image"), img, self.shape[0] * self.shape[1])
+        self._upload(self._bs("set_image"), img, int(np.prod(self.shape)))
 
     def get_coeff(self, num):
         self._need_coeffs("get_coeff")
@@ -142,8 +148,7 @@ class BoundaryWavelets2D(_BandStatsAPI):
 
     def set_coeff(self, arr, num):
         """Overwrite one band (numpy array or device tensor).  Allowed in every state but W_CREATION_ERROR; the state stays."""
-        r, c = self.coeff_shape(num)
-        self._upload(self._bs("set_coeff"), arr, r * c, int(num))
+        self._upload(self._bs("set_coeff"), arr, int(np.prod(self.coeff_shape(num))), int(num))
 
     @property
     def coeffs(self):
@@ -208,3 +213,50 @@ class BoundaryWavelets1D(BoundaryWavelets2D):
         """True when ``forward()`` and ``inverse()`` of this instance are one kernel launch each (the rows fit the LDS of a workgroup);
         False: one launch per level."""
         return bool(self._bs("fused")(self._h))
+
+
+class BoundaryWavelets3D(BoundaryWavelets2D):
+    """BoundaryWavelets3D(vol, wname, levels, mode="symmetric", dtype=None): the 3-D DWT of a volume with the same boundary modes.
+    ``vol`` is a 3-D ``(Nz, Nr, Nc)`` numpy array or a contiguous float32 / float64 device tensor.  One level runs along x (the last
+    axis), then y, then z and gives eight bands of ``(n + hlen - 1) // 2`` per axis: the bands of ``pywt.wavedecn(vol, wname, mode,
+    levels)`` in the order of ``Wavelets3D``, ``[A_L, the 7 details of level L, ..., those of level 1]``, the details of a level in
+    ``BAND_KEYS`` order (first letter = z axis).  Levels are clamped to ilog2(min(Nz, Nr, Nc) / (hlen - 1)) and to 13; Nz <= 65535 and
+    Nr * Nc < 2^31.  Same surface and state machine as ``BoundaryWavelets2D``; the finest diagonal band of the statistics is ``ddd`` of
+    level 1 and N of the universal threshold is Nz * Nr * Nc."""
+
+    _hpfx = "pdwt_bw3_"
+    _info_t = N.InfoBW3
+
+    @staticmethod
+    def _shape2(shape):
+        if len(shape) != 3:
+            raise ValueError("BoundaryWavelets3D needs a 3-D volume (Nz, Nr, Nc)")
+        return shape
+
+    def coeff_shape(self, num):
+        z, r, c = C.c_int(), C.c_int(), C.c_int()
+        if self._bs("coeff_shape")(self._h, int(num), C.byref(z), C.byref(r), C.byref(c)) <= 0:
+            raise IndexError(num)
+        return z.value, r.value, c.value
+
+    band_shape = coeff_shape
+
+    def band_index(self, level, key):
+        """Index of detail band ``key`` (e.g. "dad") of ``level`` (1 = finest)."""
+        L = self.levels
+        if not 1 <= level <= L:
+            raise IndexError(level)
+        return 1 + 7 * (L - level) + BAND_KEYS.index(key)
+
+    def get_image(self):
+        out = np.empty(self.shape, dtype=self.dtype)
+        if self._bs("get_image")(self._h, out.ctypes.data_as(C.c_void_p)) != min(out.size, 2**31 - 1):
+            raise RuntimeError("get_image failed (state=%d)" % self.state)
+        return out
+
+    def get_coeff(self, num):
+        self._need_coeffs("get_coeff")
+        out = np.empty(self.coeff_shape(num), dtype=self.dtype)
+        if self._bs("get_coeff")(self._h, out.ctypes.data_as(C.c_void_p), int(num)) != min(out.size, 2**31 - 1):
+            raise RuntimeError("get_coeff(%d) failed (state=%d)" % (num, self.state))
+        return out
