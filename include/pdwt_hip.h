@@ -590,6 +590,66 @@ int pdwt_ext3d_forward_level_f64(const double* d_src, double* const* d_bands, in
 int pdwt_ext3d_inverse_level_f32(float* d_dst, float* const* d_bands, int nz, int nr, int nc, const pdwt_filters_f32* f, float* d_tmp);
 int pdwt_ext3d_inverse_level_f64(double* d_dst, double* const* d_bands, int nz, int nr, int nc, const pdwt_filters_f64* f, double* d_tmp);
 
+/* ---------------------------------------------------------------------------------------------
+ * Batched 1-D wavelet packets (pdwt_amd/csrc/wpt1d.hip; the class: WaveletPackets1D, include/wpt1d.h): the full binary tree of
+ * every row of an Nr x Nc batch -- pywt.WaveletPacket(mode='periodization'), natural (Paley) order.  Depth l has 2^l nodes per row
+ * of n_l = div2(n_{l-1}) samples (n_0 = Nc); node i has the children 2i (a) and 2i + 1 (d) of depth l + 1: the [A, D] bands of one
+ * level of the periodised batched 1-D transform of the drivers above applied to that node (the same arithmetic; hlen == 2: the 1-D
+ * Haar level).  Node 0 of depth l is A_l and node 1 is D_l of the ordinary transform.
+ * Storage: ONE allocation per depth l = 1 .. L laid out (Nr, 2^l, n_l) row-major -- a row's depth-l line is one contiguous run of
+ * 2^l * n_l elements, a node is a strided (Nr, n_l) view with a pitch of 2^l * n_l elements.  Depth 0 is the batch.
+ *
+ * No device needed.  geometry: the depth a batch of rows of Nc samples gets (levels < 1 asks for 1; clamped to
+ * ilog2(Nc / (hlen - 1)) and to 12; 0 = too small, a bad Nc or a bad bank length) and, in n when given, n_0 .. n_L.  fused: 1 when
+ * the whole tree of a row runs in one launch (ONE row's two LDS lines of adjacent depths, halos included, fit 160 KiB in both
+ * directions: float32 rows up to about 20 000 samples, float64 about 10 000), else 0; PDWT_EINVAL when geometry gives 0 or elem_size
+ * is not 4 or 8.  tmp_elems: the scratch the whole-transform entries need, which is 0 on both paths (kept for callers that size
+ * buffers as for the boundary-mode entries); PDWT_EINVAL as fused, or for Nr < 1 or Nr * Nc >= 2^31.  frequency_order:
+ * out[r] = r ^ (r >> 1), the natural index of the node of frequency rank r (Gray code; depth 0 .. 12).  state_table: the node states
+ * of the inverse from a basis given as n (depth, idx) pairs, one byte per node, node i of depth l at (2^l - 1) + i, 2^(levels + 1)
+ * bytes: 1 = a node of the basis (loaded), 2 = above the basis (synthesised from its children), 0 = below it (skipped);
+ * PDWT_EINVAL unless every root-to-leaf path meets exactly one of the nodes.
+ *
+ * Device entries; an even f->hlen of 2 .. 40; anything out of range, or a NULL pointer, is PDWT_EINVAL and nothing is launched.
+ * Buffers need only be aligned to their element type.  Asynchronous on the library stream unless stated.
+ * The level entries run ONE depth step of nnodes (1 .. 4096) parents of n samples per row in one launch: forward reads d_parent
+ * (nr, nnodes, n) and writes d_child (nr, 2 * nnodes, div2(n)); inverse reads d_child and writes the parents named by d_list, a
+ * DEVICE array of count parent indices, or all nnodes when d_list is NULL.  nr * nnodes * n < 2^32.
+ * The whole-transform entries take d_nodes, a HOST table of levels device pointers (d_nodes[l - 1] = the allocation of depth l);
+ * levels must be what geometry gives for it.  forward fills every depth and leaves d_src intact.  inverse reconstructs d_dst
+ * (nr x nc) under d_state, the DEVICE copy of a state_table whose root is 2.  They return PDWT_WP1_FUSED when one launch ran the
+ * whole tree -- the inverse then writes d_dst ONLY -- or PDWT_WP1_LEVELS when the level kernels were looped -- the inverse then
+ * writes every synthesised parent to its own allocation first; the nodes of the basis are never modified.  Same bits on both paths.
+ * moments: out[4 * s + 0..3] = sum |c|, sum c^2, max |c|, -sum c^2 ln c^2 (zero terms skipped) of each of nseg contiguous segments
+ * of n elements (a depth: nseg = nr * 2^l, segment s = row * 2^l + node), on the HOST; accumulated in double and combined in a
+ * fixed order (no atomics: two runs give the same bits); nseg * n < 2^32.  SYNCHRONISES.
+ * thresh: op 0 soft / 1 hard threshold (the formulas of pdwt_soft_thresh / pdwt_hard_thresh) in place on the elements of d_level
+ * (nr, nnodes, n) whose node has d_flags[node] == 1 (DEVICE bytes, so a slice of a state_table serves).
+ * pdwt_memcpy2d: height rows of width BYTES between pitched buffers (pitches in bytes, width <= both); kind 0 host to device,
+ * 1 device to host (both synchronise), 2 device to device (asynchronous), 3 device to device from a foreign producer (waits for
+ * the NULL stream first and for the copy).
+ * ------------------------------------------------------------------------------------------- */
+#define PDWT_WP1_LEVELS 0 /* the per-level kernels ran */
+#define PDWT_WP1_FUSED 1  /* one launch ran the whole tree */
+int pdwt_wp1_geometry(int Nc, int hlen, int levels, int* n);
+int pdwt_wp1_fused(int Nc, int hlen, int levels, int elem_size);
+long long pdwt_wp1_tmp_elems(int Nr, int Nc, int hlen, int levels, int elem_size);
+int pdwt_wp1_frequency_order(int depth, int* out);
+int pdwt_wp1_state_table(int levels, const int* depth, const int* idx, int n, unsigned char* out);
+int pdwt_memcpy2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, int kind);
+int pdwt_wp1_forward_level_f32(const float* d_parent, float* d_child, int nr, int nnodes, int n, const pdwt_filters_f32* f);
+int pdwt_wp1_forward_level_f64(const double* d_parent, double* d_child, int nr, int nnodes, int n, const pdwt_filters_f64* f);
+int pdwt_wp1_inverse_level_f32(float* d_parent, const float* d_child, int nr, int nnodes, int n, const int* d_list, int count, const pdwt_filters_f32* f);
+int pdwt_wp1_inverse_level_f64(double* d_parent, const double* d_child, int nr, int nnodes, int n, const int* d_list, int count, const pdwt_filters_f64* f);
+int pdwt_wp1_forward_f32(const float* d_src, float* const* d_nodes, int nr, int nc, int levels, const pdwt_filters_f32* f);
+int pdwt_wp1_forward_f64(const double* d_src, double* const* d_nodes, int nr, int nc, int levels, const pdwt_filters_f64* f);
+int pdwt_wp1_inverse_f32(float* d_dst, float* const* d_nodes, int nr, int nc, int levels, const unsigned char* d_state, const pdwt_filters_f32* f);
+int pdwt_wp1_inverse_f64(double* d_dst, double* const* d_nodes, int nr, int nc, int levels, const unsigned char* d_state, const pdwt_filters_f64* f);
+int pdwt_wp1_moments_f32(const float* d_level, long long nseg, int n, double* out);
+int pdwt_wp1_moments_f64(const double* d_level, long long nseg, int n, double* out);
+int pdwt_wp1_thresh_f32(int op, float* d_level, int nr, int nnodes, int n, const unsigned char* d_flags, float beta);
+int pdwt_wp1_thresh_f64(int op, double* d_level, int nr, int nnodes, int n, const unsigned char* d_flags, double beta);
+
 #ifdef __cplusplus
 }
 #endif

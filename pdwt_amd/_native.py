@@ -23,6 +23,11 @@ class InfoWPT(C.Structure):
     _fields_ = [("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int)]
 
 
+class InfoWPT1(C.Structure):
+    """== w_info_wpt1 (include/wpt1d.h)."""
+    _fields_ = [("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int)]
+
+
 class InfoBW(C.Structure):
     """== w_info_bw (include/wt_ext.h)."""
     _fields_ = [("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int), ("mode", C.c_int)]
@@ -74,7 +79,8 @@ PLAIN_SYMBOLS = ["pdwt_device_count", "pdwt_set_device", "pdwt_get_device", "pdw
                  "pdwt_sum_scratch_doubles", "pdwt_sum_scratch_read", "pdwt_num_bands3d", "pdwt_band_size3d", "pdwt_tmp_elems3d",
                  "pdwt_num_bands_swt3d", "pdwt_band_size_swt3d", "pdwt_tmp_elems_swt3d", "pdwt_num_bands_ext", "pdwt_ext_band_shape",
                  "pdwt_num_bands_ext1d", "pdwt_ext1d_band_len", "pdwt_ext1d_fused", "pdwt_ext1d_tmp_elems",
-                 "pdwt_num_bands_ext3d", "pdwt_ext3d_band_shape", "pdwt_ext3d_tmp_elems", "pdwt_ext3d_tmp_approx_offset"]
+                 "pdwt_num_bands_ext3d", "pdwt_ext3d_band_shape", "pdwt_ext3d_tmp_elems", "pdwt_ext3d_tmp_approx_offset",
+                 "pdwt_wp1_geometry", "pdwt_wp1_fused", "pdwt_wp1_tmp_elems", "pdwt_wp1_frequency_order", "pdwt_wp1_state_table", "pdwt_memcpy2d"]
 TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coeffs_buffer", "copy_coeffs_buffer",
                   "soft_thresh", "soft_thresh_sum", "norm1", "norm1_as_double", "norm1_enqueue", "hard_thresh", "proj_linf", "shrink", "group_soft_thresh",
                   "norm2sq", "norm2sq_as_double", "add_coeffs", "circshift", "forward_nonseparable", "inverse_nonseparable",
@@ -84,7 +90,8 @@ TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coe
                   "soft_thresh_swt3d", "hard_thresh_swt3d", "norm1_swt3d", "bandlist_stats", "bandlist_thresh", "bandbatch_stats", "bandbatch_thresh",
                   "wpt2d_forward_level", "wpt2d_inverse_level", "wpt2d_node_cost", "ext2d_forward_level", "ext2d_inverse_level",
                   "ext1d_forward_level", "ext1d_inverse_level", "ext1d_forward", "ext1d_inverse",
-                  "ext3d_forward_level", "ext3d_inverse_level"] + DRIVERS + HAAR_DRIVERS)
+                  "ext3d_forward_level", "ext3d_inverse_level",
+                  "wp1_forward_level", "wp1_inverse_level", "wp1_forward", "wp1_inverse", "wp1_moments", "wp1_thresh"] + DRIVERS + HAAR_DRIVERS)
 
 _hip = None
 _host = {}
@@ -229,6 +236,21 @@ def hip():
         # volumes with boundary modes, one level: (volume, HOST table of the 8 band pointers aaa .. ddd, nz, nr, nc, [mode,] bank, scratch)
         getattr(L, "pdwt_ext3d_forward_level_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, C.POINTER(FT), vp]
         getattr(L, "pdwt_ext3d_inverse_level_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, C.POINTER(FT), vp]
+        # batched 1-D wavelet packets: one depth step (parents, children, nr, nnodes, n, [device list or NULL, count,] bank); the whole
+        # tree (src or dst, HOST table of `levels` device pointers, nr, nc, levels, [device state table,] bank) -> 1 fused / 0 per level / < 0
+        getattr(L, "pdwt_wp1_forward_level_" + sfx).argtypes = [vp, vp, ci, ci, ci, C.POINTER(FT)]
+        getattr(L, "pdwt_wp1_inverse_level_" + sfx).argtypes = [vp, vp, ci, ci, ci, vp, ci, C.POINTER(FT)]
+        getattr(L, "pdwt_wp1_forward_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, C.POINTER(FT)]
+        getattr(L, "pdwt_wp1_inverse_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, vp, C.POINTER(FT)]
+        getattr(L, "pdwt_wp1_moments_" + sfx).argtypes = [vp, C.c_longlong, ci, C.POINTER(C.c_double)]
+        getattr(L, "pdwt_wp1_thresh_" + sfx).argtypes = [ci, vp, ci, ci, ci, vp, ct]
+    L.pdwt_wp1_geometry.argtypes = [ci, ci, ci, C.POINTER(ci)]
+    L.pdwt_wp1_fused.argtypes = [ci, ci, ci, ci]
+    L.pdwt_wp1_tmp_elems.restype = C.c_longlong
+    L.pdwt_wp1_tmp_elems.argtypes = [ci, ci, ci, ci, ci]
+    L.pdwt_wp1_frequency_order.argtypes = [ci, C.POINTER(ci)]
+    L.pdwt_wp1_state_table.argtypes = [ci, C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(C.c_ubyte)]
+    L.pdwt_memcpy2d.argtypes = [vp, sz, vp, sz, sz, sz, ci]
     L.pdwt_num_bands_ext3d.argtypes = [ci, ci, ci, ci, ci]
     L.pdwt_ext3d_band_shape.restype = C.c_longlong
     L.pdwt_ext3d_band_shape.argtypes = [ci, ci, ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci), C.POINTER(ci)]
@@ -373,6 +395,36 @@ def host(dtype):
         L.pdwt_wpt_node_stats.argtypes = [vp, ci, C.POINTER(BandStats)]
         L.pdwt_wpt_estimate_sigma.restype = C.c_double
         L.pdwt_wpt_estimate_sigma.argtypes = [vp]
+        # WaveletPackets1D (include/wpt1d.h, wpt1d.cpp)
+        L.pdwt_wp1h_new.restype = vp
+        L.pdwt_wp1h_new.argtypes = [vp, ci, ci, C.c_char_p, ci, ci]
+        for n in ("delete", "forward", "inverse", "state", "basis_size", "fused"):
+            getattr(L, "pdwt_wp1h_" + n).argtypes = [vp]
+        L.pdwt_wp1h_get_image.argtypes = [vp, vp]
+        L.pdwt_wp1h_set_image.argtypes = [vp, vp, ci]
+        L.pdwt_wp1h_info.argtypes = [vp, C.POINTER(InfoWPT1)]
+        L.pdwt_wp1h_node_shape.restype = C.c_longlong
+        L.pdwt_wp1h_node_shape.argtypes = [vp, ci, pi, pi]
+        L.pdwt_wp1h_path_index.argtypes = [C.c_char_p, pi]
+        L.pdwt_wp1h_geometry.argtypes = [ci, ci, ci, pi]
+        L.pdwt_wp1h_frequency_order.argtypes = [ci, pi]
+        L.pdwt_wp1h_get_node.argtypes = [vp, vp, ci, ci]
+        L.pdwt_wp1h_get_level.restype = C.c_longlong
+        L.pdwt_wp1h_get_level.argtypes = [vp, vp, ci]
+        L.pdwt_wp1h_set_node.argtypes = [vp, vp, ci, ci, ci]
+        L.pdwt_wp1h_node_int_ptr.restype = C.c_ssize_t
+        L.pdwt_wp1h_node_int_ptr.argtypes = [vp, ci, ci, C.POINTER(C.c_longlong)]
+        L.pdwt_wp1h_node_costs.argtypes = [vp, ci, ci, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.pdwt_wp1h_best_basis.argtypes = [vp, ci]
+        L.pdwt_wp1h_set_basis.argtypes = [vp, pi, pi, ci]
+        L.pdwt_wp1h_get_basis.argtypes = [vp, pi, pi]
+        for n in ("soft_threshold", "hard_threshold"):
+            getattr(L, "pdwt_wp1h_" + n).argtypes = [vp, ct, ci]
+        L.pdwt_wp1h_norm1.restype = C.c_double
+        L.pdwt_wp1h_norm1.argtypes = [vp]
+        L.pdwt_wp1h_node_stats.argtypes = [vp, ci, C.POINTER(BandStats)]
+        L.pdwt_wp1h_estimate_sigma.restype = C.c_double
+        L.pdwt_wp1h_estimate_sigma.argtypes = [vp]
         # BoundaryWavelets (include/wt_ext.h, wt_ext.cpp)
         L.pdwt_bw_new.restype = vp
         L.pdwt_bw_new.argtypes = [vp, ci, ci, C.c_char_p, ci, ci, ci]
