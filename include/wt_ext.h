@@ -36,32 +36,23 @@ struct w_info_bw {
     int mode;
 };
 
-class BoundaryWavelets {
+/* What the three classes of this header share: every member but `winfos`, and every method whose signature does not name the number of
+ * axes.  Written once in pdwt_amd/csrc/wt_ext.cpp; what differs between the classes is one `bw_ops` table each.  Not for direct use. */
+struct bw_ops;
+class BoundaryTransform {
   public:
-    DTYPE* d_image;   /* device: image / reconstruction */
-    DTYPE** d_coeffs; /* HOST table of 3L+1 device pointers into one allocation */
+    DTYPE* d_image;   /* device: the input / its reconstruction */
+    DTYPE** d_coeffs; /* HOST table of num_bands() device pointers into one allocation */
     char wname[128];
-    w_info_bw winfos;
     w_state state;
-
-    BoundaryWavelets(DTYPE* img, int Nr, int Nc, const char* wname, int levels, int mode, int memisonhost = 1);
-    ~BoundaryWavelets();
 
     void forward();
     void inverse();
     int get_image(DTYPE* img);
     void set_image(DTYPE* img, int mem_is_on_device = 0);
 
-    /* the levels an instance of this size gets (levels < 1 asks for 1; clamped to ilog2(min(Nr, Nc) / (hlen - 1)) and BW_MAX_LEVELS;
-     * 0 = too small or a bad size / bank length) and, in nr / nc when given, the shape of the approximation of level 0 (the image) ..
-     * that level: the bands of level l are nr[l] x nc[l].  Needs no device.  What the constructor uses. */
-    static int geometry(int Nr, int Nc, int hlen, int levels, int* nr, int* nc);
-    /* the mode number of a PyWavelets mode name, -1 for any other */
-    static int mode_index(const char* name);
-
-    int num_bands() const;                                /* 3L+1; 0 after W_CREATION_ERROR */
-    long long coeff_shape(int num, int* nr, int* nc) const; /* elements of band num, 0 for a bad index */
-    int get_coeff(DTYPE* coeff, int num);                 /* elements copied, 0 when refused */
+    int num_bands() const;                /* 3L+1 (2-D), L+1 (1-D), 7L+1 (3-D); 0 after W_CREATION_ERROR */
+    int get_coeff(DTYPE* coeff, int num); /* elements copied, 0 when refused */
     void set_coeff(DTYPE* coeff, int num, int mem_is_on_device = 0);
     intptr_t image_int_ptr();
     intptr_t coeff_int_ptr(int num);
@@ -71,18 +62,44 @@ class BoundaryWavelets {
     void hard_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
     double norm1(); /* sum |c| over all bands, in double; -1 when refused */
 
-    /* the additions of wt.h on these bands (finest diagonal band = D1, N of the universal threshold = Nr * Nc), same meaning */
+    /* the additions of wt.h on these bands (the finest diagonal band and N of the universal threshold: see each class), same meaning */
     int band_stats(int num, w_band_stats* out, int with_median = 1);
     int all_band_stats(w_band_stats* out, int with_median = 0);
     double estimate_sigma();
     void threshold_bands(const DTYPE* betas, int kind = 0);
     double denoise(int method, double sigma = -1.0, int kind = 0, DTYPE* betas_out = NULL);
 
+  protected:
+    BoundaryTransform();
+    ~BoundaryTransform();
+    /* the constructor of all three: dims = {Nz, Nr, Nc} (1 for an axis the class does not have); *nlevels holds the levels asked for and
+     * gets the clamped ones, *hlen the length of the bank, as far as the construction came */
+    void create(const bw_ops& ops, DTYPE* src, const int* dims, const char* wname, int mode, int memisonhost, int* nlevels, int* hlen);
+    long long band_shape(int num, int* shape) const; /* elements of band num and its {nz, nr, nc}; 0 for a bad index */
+    const bw_ops* ops_;                              /* which of the three transforms this is */
+    void* priv_;                                     /* bank, device, geometry, the band allocation, the scratch */
+
   private:
-    void* priv_; /* bank, device, geometry, the ping buffers */
     void threshold(int op, DTYPE beta, int do_thresh_appcoeffs);
-    BoundaryWavelets(const BoundaryWavelets&);
-    BoundaryWavelets& operator=(const BoundaryWavelets&);
+    BoundaryTransform(const BoundaryTransform&);
+    BoundaryTransform& operator=(const BoundaryTransform&);
+};
+
+class BoundaryWavelets : public BoundaryTransform {
+  public:
+    w_info_bw winfos;
+
+    BoundaryWavelets(DTYPE* img, int Nr, int Nc, const char* wname, int levels, int mode, int memisonhost = 1);
+
+    /* the levels an instance of this size gets (levels < 1 asks for 1; clamped to ilog2(min(Nr, Nc) / (hlen - 1)) and BW_MAX_LEVELS;
+     * 0 = too small or a bad size / bank length) and, in nr / nc when given, the shape of the approximation of level 0 (the image) ..
+     * that level: the bands of level l are nr[l] x nc[l].  Needs no device.  What the constructor uses. */
+    static int geometry(int Nr, int Nc, int hlen, int levels, int* nr, int* nc);
+    /* the mode number of a PyWavelets mode name, -1 for any other */
+    static int mode_index(const char* name);
+
+    /* elements of band num, 0 for a bad index.  The finest diagonal band is D1 (band 3), N of the universal threshold Nr * Nc. */
+    long long coeff_shape(int num, int* nr, int* nc) const;
 };
 
 /*
@@ -96,49 +113,18 @@ class BoundaryWavelets {
  * buffer of two level-1 approximations, which only such an instance allocates.  Both paths give the same bits.
  * Statistics.  The finest detail band is band 1 (all rows together); N of the universal threshold is Nc, the batched-1-D rule of wt.h.
  */
-class BoundaryWavelets1D {
+class BoundaryWavelets1D : public BoundaryTransform {
   public:
-    DTYPE* d_image;   /* device: the batch / its reconstruction, Nr x Nc */
-    DTYPE** d_coeffs; /* HOST table of L+1 device pointers into one allocation */
-    char wname[128];
     w_info_bw winfos;
-    w_state state;
 
     BoundaryWavelets1D(DTYPE* img, int Nr, int Nc, const char* wname, int levels, int mode, int memisonhost = 1);
-    ~BoundaryWavelets1D();
-
-    void forward();
-    void inverse();
-    int get_image(DTYPE* img);
-    void set_image(DTYPE* img, int mem_is_on_device = 0);
 
     /* the levels a row of Nc samples gets (levels < 1 asks for 1; clamped to ilog2(Nc / (hlen - 1)) and BW_MAX_LEVELS; 0 = too short or
      * a bad size / bank length) and, in n when given, the samples per row of level 0 (the batch) .. that level.  Needs no device. */
     static int geometry(int Nc, int hlen, int levels, int* n);
 
-    int num_bands() const;                                /* L+1; 0 after W_CREATION_ERROR */
     long long coeff_shape(int num, int* nr, int* nc) const; /* elements of band num (Nr x N_l), 0 for a bad index */
-    int get_coeff(DTYPE* coeff, int num);
-    void set_coeff(DTYPE* coeff, int num, int mem_is_on_device = 0);
-    intptr_t image_int_ptr();
-    intptr_t coeff_int_ptr(int num);
     int fused() const; /* 1: forward() and inverse() of this instance are one launch each; 0 after W_CREATION_ERROR */
-
-    void soft_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
-    void hard_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
-    double norm1();
-
-    int band_stats(int num, w_band_stats* out, int with_median = 1);
-    int all_band_stats(w_band_stats* out, int with_median = 0);
-    double estimate_sigma();
-    void threshold_bands(const DTYPE* betas, int kind = 0);
-    double denoise(int method, double sigma = -1.0, int kind = 0, DTYPE* betas_out = NULL);
-
-  private:
-    void* priv_; /* bank, device, geometry, the scratch of the per-level path */
-    void threshold(int op, DTYPE beta, int do_thresh_appcoeffs);
-    BoundaryWavelets1D(const BoundaryWavelets1D&);
-    BoundaryWavelets1D& operator=(const BoundaryWavelets1D&);
 };
 
 /*
@@ -164,50 +150,18 @@ struct w_info_bw3 {
     int mode;
 };
 
-class BoundaryWavelets3D {
+class BoundaryWavelets3D : public BoundaryTransform {
   public:
-    DTYPE* d_image;   /* device: the volume / its reconstruction */
-    DTYPE** d_coeffs; /* HOST table of 7L+1 device pointers into one allocation */
-    char wname[128];
     w_info_bw3 winfos;
-    w_state state;
 
     BoundaryWavelets3D(DTYPE* vol, int Nz, int Nr, int Nc, const char* wname, int levels, int mode, int memisonhost = 1);
-    ~BoundaryWavelets3D();
-
-    void forward();
-    void inverse();
-    int get_image(DTYPE* vol);
-    void set_image(DTYPE* vol, int mem_is_on_device = 0);
 
     /* the levels a volume of this size gets (levels < 1 asks for 1; clamped to ilog2(min(Nz, Nr, Nc) / (hlen - 1)) and
      * BW3_MAX_LEVELS; 0 = too small or a bad size / bank length) and, in nz / nr / nc when given, the shape of the approximation of
      * level 0 (the volume) .. that level: the bands of level l are nz[l] x nr[l] x nc[l].  Needs no device. */
     static int geometry(int Nz, int Nr, int Nc, int hlen, int levels, int* nz, int* nr, int* nc);
 
-    int num_bands() const;                                           /* 7L+1; 0 after W_CREATION_ERROR */
     long long coeff_shape(int num, int* nz, int* nr, int* nc) const; /* elements of band num, 0 for a bad index */
-    int get_coeff(DTYPE* coeff, int num);                            /* elements copied, 0 when refused */
-    void set_coeff(DTYPE* coeff, int num, int mem_is_on_device = 0);
-    intptr_t image_int_ptr();
-    intptr_t coeff_int_ptr(int num);
-
-    /* every detail band; the approximation only when do_thresh_appcoeffs.  One launch. */
-    void soft_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
-    void hard_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
-    double norm1(); /* sum |c| over all bands, in double; -1 when refused */
-
-    int band_stats(int num, w_band_stats* out, int with_median = 1);
-    int all_band_stats(w_band_stats* out, int with_median = 0);
-    double estimate_sigma();
-    void threshold_bands(const DTYPE* betas, int kind = 0);
-    double denoise(int method, double sigma = -1.0, int kind = 0, DTYPE* betas_out = NULL);
-
-  private:
-    void* priv_; /* bank, device, geometry, the band allocation, the scratch */
-    void threshold(int op, DTYPE beta, int do_thresh_appcoeffs);
-    BoundaryWavelets3D(const BoundaryWavelets3D&);
-    BoundaryWavelets3D& operator=(const BoundaryWavelets3D&);
 };
 
 #endif

@@ -7,25 +7,17 @@
 #include <string.h>
 #include <vector>
 
-#include "../../include/pdwt_hip.h"
 #include "../../include/wpt.h"
+#include "host_common.hpp"
 
 static_assert(sizeof(w_band_stats) == sizeof(pdwt_band_stats), "w_band_stats must mirror pdwt_band_stats");
-
-#ifndef DOUBLEPRECISION
-#define SFX(name) name##_f32
-typedef pdwt_filters_f32 wpt_filters_t;
-#else
-#define SFX(name) name##_f64
-typedef pdwt_filters_f64 wpt_filters_t;
-#endif
 
 namespace {
 constexpr int kL = WPT_MAX_LEVELS;
 inline int nnodes(int depth) { return 1 << (2 * depth); }
 
 struct wpt_priv {
-    wpt_filters_t f;
+    filters_t f;
     int dev;  // the device current at construction; every method runs there
     int nr[kL + 1], nc[kL + 1];
     std::vector<unsigned char> in_basis[kL + 1];  // per depth: 1 = the node belongs to the basis
@@ -35,21 +27,6 @@ struct wpt_priv {
     size_t ptr_off[kL + 2];
 };
 inline wpt_priv* P(void* p) { return (wpt_priv*)p; }
-
-struct DevScopeW {
-    int prev, mine;
-    explicit DevScopeW(const void* st) : prev(-1), mine(st ? ((const wpt_priv*)st)->dev : -1)
-    {
-        if (mine < 0) return;
-        prev = pdwt_get_device();
-        if (prev != mine) pdwt_set_device(mine);
-    }
-    ~DevScopeW()
-    {
-        if (mine >= 0 && prev >= 0 && prev != mine) pdwt_set_device(prev);
-    }
-};
-void report(const char* where, int rc) { printf("ERROR: WaveletPackets%s failed (code %d): %s\n", where, rc, pdwt_last_error_string()); }
 
 // flags per depth from a list of nodes; false unless the nodes partition the tree
 bool flags_from_nodes(int L, const int* depth, const int* idx, int n, std::vector<unsigned char>* flags)
@@ -72,7 +49,7 @@ bool flags_from_nodes(int L, const int* depth, const int* idx, int n, std::vecto
     return true;
 }
 }  // namespace
-#define ON_MY_DEVICE_W() DevScopeW dev_scope_(priv_)
+#define ON_MY_DEVICE_W() DevScope dev_scope_(priv_ ? ((const wpt_priv*)priv_)->dev : -1)
 
 // install flags (a valid partition): the parents above basis nodes, per depth, on the host and on the device
 static int install_basis(wpt_priv* p, int L, std::vector<unsigned char>* flags)
@@ -207,7 +184,7 @@ WaveletPackets::WaveletPackets(DTYPE* img, int Nr, int Nc, const char* wname_, i
         else rc = pdwt_memcpy_d2d_foreign(d_image, img, n * sizeof(DTYPE));
     }
     if (rc != PDWT_OK) {
-        report("(): allocation or upload", rc);
+        report("WaveletPackets", "(): allocation or upload", rc);
         state = W_CREATION_ERROR;
     }
 }
@@ -235,7 +212,7 @@ void WaveletPackets::forward()
     for (int l = 0; l < winfos.nlevels; l++) {
         const int rc = SFX(pdwt_wpt2d_forward_level)(d_nodes[l], d_nodes[l + 1], p->nr[l], p->nc[l], NULL, nnodes(l), &p->f);
         if (rc != PDWT_OK) {
-            report("::forward()", rc);
+            report("WaveletPackets", "::forward()", rc);
             state = W_FORWARD_ERROR;
             return;
         }
@@ -261,7 +238,7 @@ void WaveletPackets::inverse()
         const int* list = (n == nnodes(l)) ? NULL : p->d_lists + p->ptr_off[l];
         const int rc = SFX(pdwt_wpt2d_inverse_level)(d_nodes[l], d_nodes[l + 1], p->nr[l], p->nc[l], list, n, &p->f);
         if (rc != PDWT_OK) {
-            report("::inverse()", rc);
+            report("WaveletPackets", "::inverse()", rc);
             state = W_INVERSE_ERROR;
             return;
         }
@@ -284,7 +261,7 @@ void WaveletPackets::set_image(DTYPE* img, int mem_is_on_device)
     if (!d_image || !img || state == W_CREATION_ERROR) return;
     const size_t nb = (size_t)winfos.Nr * winfos.Nc * sizeof(DTYPE);
     const int rc = mem_is_on_device ? pdwt_memcpy_d2d_foreign(d_image, img, nb) : pdwt_memcpy_h2d(d_image, img, nb);
-    if (rc != PDWT_OK) report("::set_image()", rc);
+    if (rc != PDWT_OK) report("WaveletPackets", "::set_image()", rc);
     state = W_INIT;
 }
 
@@ -335,7 +312,7 @@ int WaveletPackets::set_node(DTYPE* in, int depth, int idx, int mem_is_on_device
     DTYPE* dst = d_nodes[depth] + (size_t)idx * n;
     const int rc = mem_is_on_device ? pdwt_memcpy_d2d_foreign(dst, in, (size_t)n * sizeof(DTYPE)) : pdwt_memcpy_h2d(dst, in, (size_t)n * sizeof(DTYPE));
     if (rc != PDWT_OK) {
-        report("::set_node()", rc);
+        report("WaveletPackets", "::set_node()", rc);
         return 0;
     }
     state = W_THRESHOLD;
@@ -355,7 +332,7 @@ int WaveletPackets::node_costs(int depth, int kind, double* out)
     const long long n = node_shape(depth, NULL, NULL);
     if (!(state == W_FORWARD || state == W_THRESHOLD) || n <= 0 || !out) return PDWT_EINVAL;
     const int rc = SFX(pdwt_wpt2d_node_cost)(d_nodes[depth], (size_t)n, nnodes(depth), kind, out);
-    if (rc != PDWT_OK) report("::node_costs()", rc);
+    if (rc != PDWT_OK) report("WaveletPackets", "::node_costs()", rc);
     return rc;
 }
 
@@ -434,7 +411,7 @@ void WaveletPackets::threshold(int op, DTYPE beta, int do_thresh_appcoeffs)
         const size_t n = (size_t)p->nr[l] * p->nc[l];
         const int rc = SFX(pdwt_bandbatch_thresh)(op, p->d_ptr + p->ptr_off[l], &n, betas.data(), nnodes(l), 1);
         if (rc != PDWT_OK) {
-            report(op ? "::hard_threshold()" : "::soft_threshold()", rc);
+            report("WaveletPackets", op ? "::hard_threshold()" : "::soft_threshold()", rc);
             state = W_THRESHOLD_ERROR;
             return;
         }
@@ -471,7 +448,7 @@ int WaveletPackets::node_stats(int depth, w_band_stats* out)
     wpt_priv* p = P(priv_);
     const size_t ne = (size_t)n;
     const int rc = SFX(pdwt_bandbatch_stats)(p->d_ptr + p->ptr_off[depth], &ne, nnodes(depth), 1, NULL, reinterpret_cast<pdwt_band_stats*>(out));
-    if (rc != PDWT_OK) report("::node_stats()", rc);
+    if (rc != PDWT_OK) report("WaveletPackets", "::node_stats()", rc);
     return rc;
 }
 
@@ -486,7 +463,7 @@ double WaveletPackets::estimate_sigma()
     pdwt_band_stats s;
     const int rc = SFX(pdwt_bandlist_stats)(&d, &n, 1, &want, &s);
     if (rc != PDWT_OK) {
-        report("::estimate_sigma()", rc);
+        report("WaveletPackets", "::estimate_sigma()", rc);
         return -1.0;
     }
     return s.median_abs / 0.6744897501960817;

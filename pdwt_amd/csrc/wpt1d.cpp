@@ -8,18 +8,10 @@
 #include <string.h>
 #include <vector>
 
-#include "../../include/pdwt_hip.h"
 #include "../../include/wpt1d.h"
+#include "host_common.hpp"
 
 static_assert(sizeof(w_band_stats) == sizeof(pdwt_band_stats), "w_band_stats must mirror pdwt_band_stats");
-
-#ifndef DOUBLEPRECISION
-#define SFX(name) name##_f32
-typedef pdwt_filters_f32 wp1_filters_t;
-#else
-#define SFX(name) name##_f64
-typedef pdwt_filters_f64 wp1_filters_t;
-#endif
 
 namespace {
 constexpr int kL = WPT1D_MAX_LEVELS;
@@ -27,7 +19,7 @@ inline int nnodes(int depth) { return 1 << depth; }
 inline size_t toff(int depth) { return ((size_t)1 << depth) - 1; }  // where depth l starts in the node tables
 
 struct wp1_priv {
-    wp1_filters_t f;
+    filters_t f;
     int dev;  // the device current at construction; every method runs there
     int n[kL + 1];
     int fused;
@@ -37,21 +29,6 @@ struct wp1_priv {
     unsigned char* d_thr;                         // device: 1 = a basis node other than the all-"a" node of its depth
 };
 inline wp1_priv* P(void* p) { return (wp1_priv*)p; }
-
-struct DevScopeP {
-    int prev, mine;
-    explicit DevScopeP(const void* st) : prev(-1), mine(st ? ((const wp1_priv*)st)->dev : -1)
-    {
-        if (mine < 0) return;
-        prev = pdwt_get_device();
-        if (prev != mine) pdwt_set_device(mine);
-    }
-    ~DevScopeP()
-    {
-        if (mine >= 0 && prev >= 0 && prev != mine) pdwt_set_device(prev);
-    }
-};
-void report(const char* where, int rc) { printf("ERROR: WaveletPackets1D%s failed (code %d): %s\n", where, rc, pdwt_last_error_string()); }
 
 // install a basis given as pairs: the state table (which validates the partition), the flags, and both on the device
 int install_basis(wp1_priv* p, int L, const int* depth, const int* idx, int n)
@@ -71,7 +48,7 @@ int install_basis(wp1_priv* p, int L, const int* depth, const int* idx, int n)
     return PDWT_OK;
 }
 }  // namespace
-#define ON_MY_DEVICE_P() DevScopeP dev_scope_(priv_)
+#define ON_MY_DEVICE_P() DevScope dev_scope_(priv_ ? ((const wp1_priv*)priv_)->dev : -1)
 
 int WaveletPackets1D::geometry(int Nc, int hlen, int levels, int* n) { return pdwt_wp1_geometry(Nc, hlen, levels, n); }
 
@@ -159,7 +136,7 @@ WaveletPackets1D::WaveletPackets1D(DTYPE* rows, int Nr, int Nc, const char* wnam
         else rc = pdwt_memcpy_d2d_foreign(d_image, rows, n * sizeof(DTYPE));
     }
     if (rc != PDWT_OK) {
-        report("(): allocation or upload", rc);
+        report("WaveletPackets1D", "(): allocation or upload", rc);
         state = W_CREATION_ERROR;
     }
 }
@@ -188,7 +165,7 @@ void WaveletPackets1D::forward()
     wp1_priv* p = P(priv_);
     const int rc = SFX(pdwt_wp1_forward)(d_image, d_nodes + 1, winfos.Nr, winfos.Nc, winfos.nlevels, &p->f);
     if (rc < 0) {
-        report("::forward()", rc);
+        report("WaveletPackets1D", "::forward()", rc);
         state = W_FORWARD_ERROR;
         return;
     }
@@ -210,7 +187,7 @@ void WaveletPackets1D::inverse()
     if (!p->in_basis[0][0]) {  // (the batch itself as the basis: nothing to synthesise)
         const int rc = SFX(pdwt_wp1_inverse)(d_image, d_nodes + 1, winfos.Nr, winfos.Nc, winfos.nlevels, p->d_state, &p->f);
         if (rc < 0) {
-            report("::inverse()", rc);
+            report("WaveletPackets1D", "::inverse()", rc);
             state = W_INVERSE_ERROR;
             return;
         }
@@ -233,7 +210,7 @@ void WaveletPackets1D::set_image(DTYPE* rows, int mem_is_on_device)
     if (!d_image || !rows || state == W_CREATION_ERROR) return;
     const size_t nb = (size_t)winfos.Nr * winfos.Nc * sizeof(DTYPE);
     const int rc = mem_is_on_device ? pdwt_memcpy_d2d_foreign(d_image, rows, nb) : pdwt_memcpy_h2d(d_image, rows, nb);
-    if (rc != PDWT_OK) report("::set_image()", rc);
+    if (rc != PDWT_OK) report("WaveletPackets1D", "::set_image()", rc);
     state = W_INIT;
 }
 
@@ -296,7 +273,7 @@ int WaveletPackets1D::set_node(DTYPE* in, int depth, int idx, int mem_is_on_devi
     const size_t w = (size_t)P(priv_)->n[depth] * sizeof(DTYPE);
     const int rc = pdwt_memcpy2d((void*)dst, (size_t)pitch * sizeof(DTYPE), in, w, w, (size_t)winfos.Nr, mem_is_on_device ? 3 : 0);
     if (rc != PDWT_OK) {
-        report("::set_node()", rc);
+        report("WaveletPackets1D", "::set_node()", rc);
         return 0;
     }
     state = W_THRESHOLD;
@@ -318,7 +295,7 @@ int WaveletPackets1D::node_costs(int depth, int kind, double* out, double* per_r
     std::vector<double> m;
     const int rc = depth_moments(this, priv_, depth, m);
     if (rc != PDWT_OK) {
-        report("::node_costs()", rc);
+        report("WaveletPackets1D", "::node_costs()", rc);
         return rc;
     }
     const int nn = nnodes(depth), col = kind == 0 ? 0 : 3;
@@ -401,7 +378,7 @@ void WaveletPackets1D::threshold(int op, DTYPE beta, int do_thresh_appcoeffs)
         const unsigned char* flags = (do_thresh_appcoeffs ? p->d_state : p->d_thr) + toff(l);
         const int rc = SFX(pdwt_wp1_thresh)(op, d_nodes[l], winfos.Nr, nnodes(l), p->n[l], flags, beta);
         if (rc != PDWT_OK) {
-            report(op ? "::hard_threshold()" : "::soft_threshold()", rc);
+            report("WaveletPackets1D", op ? "::hard_threshold()" : "::soft_threshold()", rc);
             state = W_THRESHOLD_ERROR;
             return;
         }
@@ -438,7 +415,7 @@ int WaveletPackets1D::node_stats(int depth, w_band_stats* out)
     std::vector<double> m;
     const int rc = depth_moments(this, priv_, depth, m);
     if (rc != PDWT_OK) {
-        report("::node_stats()", rc);
+        report("WaveletPackets1D", "::node_stats()", rc);
         return rc;
     }
     const int nn = nnodes(depth);
@@ -468,7 +445,7 @@ double WaveletPackets1D::estimate_sigma()
     if (rc == PDWT_OK) rc = SFX(pdwt_bandlist_stats)(&band, &n, 1, &want, &s);
     pdwt_free(tmp);
     if (rc != PDWT_OK) {
-        report("::estimate_sigma()", rc);
+        report("WaveletPackets1D", "::estimate_sigma()", rc);
         return -1.0;
     }
     return s.median_abs / 0.6744897501960817;

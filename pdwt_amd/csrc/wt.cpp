@@ -14,20 +14,12 @@
 #include <string.h>
 #include <strings.h>
 
-#include "../../include/pdwt_hip.h"
 #include "../../include/wt.h"
 #include "../../include/wt_batch.h"
 #include "bandstats_host.hpp"
+#include "host_common.hpp"
 
 static_assert(sizeof(w_info) == sizeof(pdwt_info), "w_info must mirror pdwt_info");
-
-#ifndef DOUBLEPRECISION
-#define SFX(name) name##_f32
-typedef pdwt_filters_f32 filters_t;
-#else
-#define SFX(name) name##_f64
-typedef pdwt_filters_f64 filters_t;
-#endif
 
 // ---- size helpers (reference src/utils.cu:4-34) ------------------------------------------------
 int w_iDivUp(int a, int b) { return (a + b - 1) / b; }
@@ -83,23 +75,9 @@ static inline void coeffs_changed(void* st)
 static inline filters_t* F(void* p) { return &((wstate_t*)p)->f; }
 static inline wstate_t* WS(void* p) { return (wstate_t*)p; }
 
-// Multi-device use from one host thread (the reference has none: TODO.txt:15): an instance belongs to the device that was
-// current at its construction; every method that touches device memory switches to that device for its duration, so
-// instances on different devices can be driven in turn (their work overlaps: launches are asynchronous).
-struct DevScope {
-    int prev, mine;
-    explicit DevScope(const void* st) : prev(-1), mine(st ? ((const wstate_t*)st)->dev : -1)
-    {
-        if (mine < 0) return;
-        prev = pdwt_get_device();
-        if (prev != mine) pdwt_set_device(mine);
-    }
-    ~DevScope()
-    {
-        if (mine >= 0 && prev >= 0 && prev != mine) pdwt_set_device(prev);
-    }
-};
-#define ON_MY_DEVICE() DevScope dev_scope_(filters_)
+// the device an instance lives on (wstate_t::dev; -1 without private state), for the guard of host_common.hpp
+static inline int dev_of(const void* st) { return st ? ((const wstate_t*)st)->dev : -1; }
+#define ON_MY_DEVICE() DevScope dev_scope_(dev_of(filters_))
 
 int w_set_device(int dev) { return pdwt_set_device(dev); }
 int w_get_device(void) { return pdwt_get_device(); }
@@ -220,7 +198,7 @@ Wavelets::Wavelets(const Wavelets& W)
       do_separable(W.do_separable), do_cycle_spinning(W.do_cycle_spinning), winfos(W.winfos), state(W.state), filters_(NULL)
 {
     memcpy(wname, W.wname, sizeof(wname));
-    DevScope dev_scope_(W.filters_);  // the copy lives on the source's device
+    DevScope dev_scope_(dev_of(W.filters_));  // the copy lives on the source's device
     if (W.filters_) {
         filters_ = calloc(1, sizeof(wstate_t));
         if (filters_) {
@@ -721,7 +699,7 @@ struct WaveletsImagesOps {
             if (rc != PDWT_OK) img[b]->state = W_THRESHOLD_ERROR;
         }
     }
-    static const void* dev_of(Wavelets* const* img, int B) { return (img && B > 0 && img[0]) ? img[0]->filters_ : NULL; }
+    static int dev_of(Wavelets* const* img, int B) { return ::dev_of((img && B > 0 && img[0]) ? img[0]->filters_ : NULL); }
 };
 
 int w_images_all_band_stats(Wavelets* const* img, int B, void** table, w_band_stats* out, int with_median)

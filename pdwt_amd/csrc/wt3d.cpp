@@ -7,19 +7,11 @@
 #include <new>
 #include <string.h>
 
-#include "../../include/pdwt_hip.h"
 #include "../../include/swt3d.h"
 #include "bandstats_host.hpp"
+#include "host_common.hpp"
 
 static_assert(sizeof(w_info3d) == sizeof(pdwt_info3d), "w_info3d must mirror pdwt_info3d");
-
-#ifndef DOUBLEPRECISION
-#define SFX(name) name##_f32
-typedef pdwt_filters_f32 filters3_t;
-#else
-#define SFX(name) name##_f64
-typedef pdwt_filters_f64 filters3_t;
-#endif
 
 // What one transform contributes to the shared class: its name in messages, its entry points of include/pdwt_hip.h in this build's
 // precision, and the two texts that differ.  The only place that knows which transform an instance runs.
@@ -28,8 +20,8 @@ struct w_ops3d {
     size_t (*tmp_elems)(pdwt_info3d);
     DTYPE** (*create_coeffs_buffer)(pdwt_info3d);
     int (*free_coeffs_buffer)(DTYPE**, pdwt_info3d);
-    int (*forward)(DTYPE*, DTYPE**, DTYPE*, pdwt_info3d, const filters3_t*);
-    int (*inverse)(DTYPE*, DTYPE**, DTYPE*, pdwt_info3d, const filters3_t*);
+    int (*forward)(DTYPE*, DTYPE**, DTYPE*, pdwt_info3d, const filters_t*);
+    int (*inverse)(DTYPE*, DTYPE**, DTYPE*, pdwt_info3d, const filters_t*);
     int (*soft_thresh)(DTYPE**, DTYPE, pdwt_info3d, int, int);
     int (*hard_thresh)(DTYPE**, DTYPE, pdwt_info3d, int, int);
     int (*norm1)(DTYPE**, pdwt_info3d, double*);
@@ -50,7 +42,7 @@ static const w_ops3d kSwtOps = {
 
 namespace {
 struct state3_t {
-    filters3_t f;
+    filters_t f;
     int dev;  // the device current at construction; every method runs there
 };
 inline state3_t* S(void* p) { return (state3_t*)p; }
@@ -60,23 +52,8 @@ inline pdwt_info3d to_pdwt3(const w_info3d& w)
     memcpy(&p, &w, sizeof(p));
     return p;
 }
-struct DevScope3 {
-    int prev, mine;
-    explicit DevScope3(const void* st) : prev(-1), mine(st ? ((const state3_t*)st)->dev : -1)
-    {
-        if (mine < 0) return;
-        prev = pdwt_get_device();
-        if (prev != mine) pdwt_set_device(mine);
-    }
-    ~DevScope3()
-    {
-        if (mine >= 0 && prev >= 0 && prev != mine) pdwt_set_device(prev);
-    }
-};
-// "ERROR: <class><where> failed ...": where = "::method()" or "(): what"
-void report3(const w_ops3d* ops, const char* where, int rc) { printf("ERROR: %s%s failed (code %d): %s\n", ops->name, where, rc, pdwt_last_error_string()); }
 }  // namespace
-#define ON_MY_DEVICE3() DevScope3 dev_scope_(filters_)
+#define ON_MY_DEVICE3() DevScope dev_scope_(filters_ ? ((const state3_t*)filters_)->dev : -1)
 
 Transform3D::Transform3D(const w_ops3d& ops, DTYPE* vol, int Nz, int Nr, int Nc, const char* wname_, int levels, int memisonhost)
     : d_image(NULL), d_coeffs(NULL), d_tmp(NULL), state(W_INIT), ops_(&ops), filters_(NULL)
@@ -145,7 +122,7 @@ Transform3D::Transform3D(const w_ops3d& ops, DTYPE* vol, int Nz, int Nr, int Nc,
     else if (memisonhost) rc = pdwt_memcpy_h2d(d_image, vol, n * sizeof(DTYPE));
     else rc = pdwt_memcpy_d2d_foreign(d_image, vol, n * sizeof(DTYPE));
     if (rc != PDWT_OK) {
-        report3(ops_, "(): volume upload", rc);
+        report(ops_->name, "(): volume upload", rc);
         state = W_CREATION_ERROR;
     }
 }
@@ -168,7 +145,7 @@ void Transform3D::forward()
     }
     const int rc = ops_->forward(d_image, d_coeffs, d_tmp, to_pdwt3(winfos), &S(filters_)->f);
     if (rc != PDWT_OK) {
-        report3(ops_, "::forward()", rc);
+        report(ops_->name, "::forward()", rc);
         state = W_FORWARD_ERROR;
         return;
     }
@@ -188,7 +165,7 @@ void Transform3D::inverse()
     }
     const int rc = ops_->inverse(d_image, d_coeffs, d_tmp, to_pdwt3(winfos), &S(filters_)->f);
     if (rc != PDWT_OK) {
-        report3(ops_, "::inverse()", rc);
+        report(ops_->name, "::inverse()", rc);
         state = W_INVERSE_ERROR;
         return;
     }
@@ -205,7 +182,7 @@ void Transform3D::soft_threshold(DTYPE beta, int do_thresh_appcoeffs, int normal
     if (state == W_CREATION_ERROR) return;
     const int rc = ops_->soft_thresh(d_coeffs, beta, to_pdwt3(winfos), do_thresh_appcoeffs, normalize);
     if (rc != PDWT_OK) {
-        report3(ops_, "::soft_threshold()", rc);
+        report(ops_->name, "::soft_threshold()", rc);
         state = W_THRESHOLD_ERROR;
     }
 }
@@ -220,7 +197,7 @@ void Transform3D::hard_threshold(DTYPE beta, int do_thresh_appcoeffs, int normal
     if (state == W_CREATION_ERROR) return;
     const int rc = ops_->hard_thresh(d_coeffs, beta, to_pdwt3(winfos), do_thresh_appcoeffs, normalize);
     if (rc != PDWT_OK) {
-        report3(ops_, "::hard_threshold()", rc);
+        report(ops_->name, "::hard_threshold()", rc);
         state = W_THRESHOLD_ERROR;
     }
 }
@@ -231,7 +208,7 @@ double Transform3D::norm1_double()
     if (state == W_CREATION_ERROR) return 0;
     double d = 0;
     const int rc = ops_->norm1(d_coeffs, to_pdwt3(winfos), &d);
-    if (rc != PDWT_OK) report3(ops_, "::norm1()", rc);
+    if (rc != PDWT_OK) report(ops_->name, "::norm1()", rc);
     return d;
 }
 DTYPE Transform3D::norm1() { return (DTYPE)norm1_double(); }
@@ -251,7 +228,7 @@ void Transform3D::set_image(DTYPE* vol, int mem_is_on_device)
     if (!d_image || !vol) return;
     const size_t nb = (size_t)winfos.Nz * winfos.Nr * winfos.Nc * sizeof(DTYPE);
     const int rc = mem_is_on_device ? pdwt_memcpy_d2d_foreign(d_image, vol, nb) : pdwt_memcpy_h2d(d_image, vol, nb);
-    if (rc != PDWT_OK) report3(ops_, "::set_image()", rc);
+    if (rc != PDWT_OK) report(ops_->name, "::set_image()", rc);
     if (state != W_CREATION_ERROR) state = W_INIT;
 }
 
@@ -292,7 +269,7 @@ void Transform3D::set_coeff(DTYPE* coeff, int num, int mem_is_on_device)
     }
     const size_t nb = (size_t)n * sizeof(DTYPE);
     const int rc = mem_is_on_device ? pdwt_memcpy_d2d_foreign(d_coeffs[num], coeff, nb) : pdwt_memcpy_h2d(d_coeffs[num], coeff, nb);
-    if (rc != PDWT_OK) report3(ops_, "::set_coeff()", rc);
+    if (rc != PDWT_OK) report(ops_->name, "::set_coeff()", rc);
 }
 
 intptr_t Transform3D::image_int_ptr(void) { return (intptr_t)d_image; }
@@ -325,7 +302,7 @@ int Transform3D::band_stats(int num, w_band_stats* out, int with_median)
     const pdwt_bl::BandList bl = band_list(*this);
     if (!bl.nb || num < 0 || num >= bl.nb || !out) return PDWT_EINVAL;
     const int rc = pdwt_bl::stats(bl, num, out, with_median);
-    if (rc != PDWT_OK) report3(ops_, "::band_stats()", rc);
+    if (rc != PDWT_OK) report(ops_->name, "::band_stats()", rc);
     return rc;
 }
 
@@ -335,7 +312,7 @@ int Transform3D::all_band_stats(w_band_stats* out, int with_median)
     const pdwt_bl::BandList bl = band_list(*this);
     if (!bl.nb || !out) return PDWT_EINVAL;
     const int rc = pdwt_bl::stats(bl, -1, out, with_median);
-    if (rc != PDWT_OK) report3(ops_, "::all_band_stats()", rc);
+    if (rc != PDWT_OK) report(ops_->name, "::all_band_stats()", rc);
     return rc;
 }
 
@@ -347,7 +324,7 @@ double Transform3D::estimate_sigma()
     if (!bl.nb) return -1.0;
     const int rc = pdwt_bl::estimate_sigma(bl, &sigma);
     if (rc != PDWT_OK) {
-        report3(ops_, "::estimate_sigma()", rc);
+        report(ops_->name, "::estimate_sigma()", rc);
         return -1.0;
     }
     return sigma;
@@ -360,7 +337,7 @@ void Transform3D::threshold_bands(const DTYPE* betas, int kind)
     if (!bl.nb || !betas || (kind != 0 && kind != 1)) return;
     const int rc = pdwt_bl::threshold(bl, betas, kind);
     if (rc != PDWT_OK) {
-        report3(ops_, "::threshold_bands()", rc);
+        report(ops_->name, "::threshold_bands()", rc);
         state = W_THRESHOLD_ERROR;
     }
 }
@@ -373,7 +350,7 @@ double Transform3D::denoise(int method, double sigma, int kind, DTYPE* betas_out
     DTYPE betas[pdwt_bl::kMaxBands];
     const int rc = pdwt_bl::denoise(bl, method, kind, &sigma, betas);
     if (rc != PDWT_OK) {
-        report3(ops_, "::denoise()", rc);
+        report(ops_->name, "::denoise()", rc);
         state = W_THRESHOLD_ERROR;
         return -1.0;
     }

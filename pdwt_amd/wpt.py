@@ -64,6 +64,14 @@ class WaveletPackets2D:
     """WaveletPackets2D(img, wname, levels, dtype=None): ``img`` is a 2-D numpy array or a contiguous float32 / float64 device tensor
     (copied device to device, as ``Wavelets`` does).  Same state machine as ``Wavelets``; device memory about (levels + 1) images."""
 
+    # what a subclass over another tree replaces: handle prefix, children per node, info struct, the two error texts that name the class
+    _hpfx, _arity, _info_t = "pdwt_wpt_", 4, N.InfoWPT
+    _err_shape = "WaveletPackets2D needs a 2-D image (Nr, Nc)"
+    _err_alloc = "WaveletPackets2D allocation failed"
+
+    def _fn(self, name):
+        return getattr(self._L, self._hpfx + name)
+
     def __init__(self, img, wname, levels, dtype=None):
         N.require_gpu()
         dev = _device_source(img)
@@ -79,18 +87,18 @@ class WaveletPackets2D:
             keep = np.ascontiguousarray(img, dtype=dt)
             shape, src, on_host = keep.shape, keep.ctypes.data_as(C.c_void_p), 1
         if len(shape) != 2:
-            raise ValueError("WaveletPackets2D needs a 2-D image (Nr, Nc)")
+            raise ValueError(self._err_shape)
         self.dtype, self.shape, self.wname = np.dtype(dt), tuple(int(v) for v in shape), wname
         self._L = N.host(self.dtype)
         self._ct = C.c_float if self.dtype == np.float32 else C.c_double
-        self._h = self._L.pdwt_wpt_new(src, self.shape[0], self.shape[1], wname.encode(), int(levels), on_host)
+        self._h = self._fn("new")(src, self.shape[0], self.shape[1], wname.encode(), int(levels), on_host)
         del keep
         if not self._h:
-            raise MemoryError("WaveletPackets2D allocation failed")
+            raise MemoryError(self._err_alloc)
 
     def close(self):
         if getattr(self, "_h", None):
-            self._L.pdwt_wpt_delete(self._h)
+            self._fn("delete")(self._h)
         self._h = None
 
     __del__ = close
@@ -98,8 +106,8 @@ class WaveletPackets2D:
     # -- introspection ---------------------------------------------------------------------
     @property
     def info(self):
-        i = N.InfoWPT()
-        self._L.pdwt_wpt_info(self._h, C.byref(i))
+        i = self._info_t()
+        self._fn("info")(self._h, C.byref(i))
         return i
 
     @property
@@ -108,17 +116,17 @@ class WaveletPackets2D:
 
     @property
     def state(self):
-        return self._L.pdwt_wpt_state(self._h)
+        return self._fn("state")(self._h)
 
     def node_shape(self, depth):
         r, c = C.c_int(), C.c_int()
-        if self._L.pdwt_wpt_node_shape(self._h, int(depth), C.byref(r), C.byref(c)) <= 0:
+        if self._fn("node_shape")(self._h, int(depth), C.byref(r), C.byref(c)) <= 0:
             raise IndexError(depth)
         return r.value, c.value
 
     def _node(self, node):
-        d, i = path_to_index(node) if isinstance(node, str) else (int(node[0]), int(node[1]))
-        if not (0 <= d <= self.levels and 0 <= i < 4 ** d):
+        d, i = path_to_index(node, self._arity) if isinstance(node, str) else (int(node[0]), int(node[1]))
+        if not (0 <= d <= self.levels and 0 <= i < self._arity ** d):
             raise IndexError(node)
         return d, i
 
@@ -128,15 +136,15 @@ class WaveletPackets2D:
 
     # -- transforms ------------------------------------------------------------------------
     def forward(self):
-        self._L.pdwt_wpt_forward(self._h)
+        self._fn("forward")(self._h)
 
     def inverse(self):
-        self._L.pdwt_wpt_inverse(self._h)
+        self._fn("inverse")(self._h)
 
     # -- data in and out -------------------------------------------------------------------
     def get_image(self):
         out = np.empty(self.shape, dtype=self.dtype)
-        if self._L.pdwt_wpt_get_image(self._h, out.ctypes.data_as(C.c_void_p)) != out.size:
+        if self._fn("get_image")(self._h, out.ctypes.data_as(C.c_void_p)) != out.size:
             raise RuntimeError("get_image failed")
         return out
 
@@ -153,13 +161,13 @@ class WaveletPackets2D:
         return fn(self._h, a.ctypes.data_as(C.c_void_p), *args, 0)
 
     def set_image(self, img):
-        self._upload(self._L.pdwt_wpt_set_image, img, self.shape[0] * self.shape[1])
+        self._upload(self._fn("set_image"), img, self.shape[0] * self.shape[1])
 
     def get_level(self, depth):
         """All nodes of ``depth`` as one array of shape (4^depth, nr, nc)."""
         self._need_coeffs("get_level")
         out = np.empty((4 ** int(depth),) + self.node_shape(depth), dtype=self.dtype)
-        if self._L.pdwt_wpt_get_level(self._h, out.ctypes.data_as(C.c_void_p), int(depth)) != out.size:
+        if self._fn("get_level")(self._h, out.ctypes.data_as(C.c_void_p), int(depth)) != out.size:
             raise RuntimeError("get_level(%d) failed (state=%d)" % (depth, self.state))
         return out
 
@@ -167,23 +175,23 @@ class WaveletPackets2D:
         self._need_coeffs("get_node")
         d, i = self._node(node)
         out = np.empty(self.node_shape(d), dtype=self.dtype)
-        if self._L.pdwt_wpt_get_node(self._h, out.ctypes.data_as(C.c_void_p), d, i) != out.size:
+        if self._fn("get_node")(self._h, out.ctypes.data_as(C.c_void_p), d, i) != out.size:
             raise RuntimeError("get_node(%r) failed (state=%d)" % (node, self.state))
         return out
 
     def set_node(self, node, arr):
-        """Overwrite one node (numpy array or device tensor); the state becomes W_THRESHOLD.  Needs the tree of a ``forward()``:
+        """Overwrite one node (dense numpy array or device tensor of ``node_shape``); the state becomes W_THRESHOLD.  Needs the tree of a ``forward()``:
         refused (``RuntimeError``) before it and after ``inverse()``."""
         if self.state not in (W_FORWARD, W_THRESHOLD):
             raise RuntimeError("set_node refused (state=%d): run forward() first" % self.state)
         d, i = self._node(node)
         r, c = self.node_shape(d)
-        if self._upload(self._L.pdwt_wpt_set_node, arr, r * c, d, i) != r * c:
+        if self._upload(self._fn("set_node"), arr, r * c, d, i) != r * c:
             raise RuntimeError("set_node(%r) failed (state=%d)" % (node, self.state))
 
     def node_int_ptr(self, node):
         d, i = self._node(node)
-        return self._L.pdwt_wpt_node_int_ptr(self._h, d, i)
+        return self._fn("node_int_ptr")(self._h, d, i)
 
     def node_view(self, node):
         """One node as a zero-copy DeviceArray (call ``sync()`` before a consumer on another stream reads it)."""
@@ -201,8 +209,8 @@ class WaveletPackets2D:
             raise ValueError("cost must be 'l1' or 'shannon'")
         out = []
         for d in range(self.levels + 1):
-            c = np.empty(4 ** d, dtype=np.float64)
-            if self._L.pdwt_wpt_node_costs(self._h, d, COSTS[cost], c.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+            c = np.empty(self._arity ** d, dtype=np.float64)
+            if self._fn("node_costs")(self._h, d, COSTS[cost], c.ctypes.data_as(C.POINTER(C.c_double))) != 0:
                 raise RuntimeError("node_costs refused (state=%d): the coefficients are not valid" % self.state)
             out.append(c)
         return out
@@ -210,60 +218,60 @@ class WaveletPackets2D:
     @property
     def basis(self):
         """The current basis as a sorted list of (depth, idx)."""
-        n = self._L.pdwt_wpt_basis_size(self._h)
+        n = self._fn("basis_size")(self._h)
         d, i = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        self._L.pdwt_wpt_get_basis(self._h, d, i)
+        self._fn("get_basis")(self._h, d, i)
         return [(d[k], i[k]) for k in range(n)]
 
     def best_basis(self, cost="shannon"):
         """Coifman-Wickerhauser search, bottom-up on the host over ``node_costs(cost)``: a parent is kept when its cost is <= the
-        sum of its children's best costs.  Installs the basis and returns it.  Needs the untouched tree of one forward()."""
+        sum of its children's best costs (1-D: costs summed over the rows).  Installs the basis and returns it.  Needs the untouched tree of one forward()."""
         if cost not in COSTS:
             raise ValueError("cost must be 'l1' or 'shannon'")
-        if self._L.pdwt_wpt_best_basis(self._h, COSTS[cost]) < 1:
+        if self._fn("best_basis")(self._h, COSTS[cost]) < 1:
             raise RuntimeError("best_basis refused (state=%d): it needs the coefficients of forward(), unmodified" % self.state)
         return self.basis
 
     def set_basis(self, nodes):
         """Install a basis: paths or (depth, idx) pairs that partition the tree (``ValueError`` otherwise)."""
-        b = check_basis(nodes, self.levels)
+        b = check_basis(nodes, self.levels, self._arity)
         if self.state == W_THRESHOLD:
             raise RuntimeError("set_basis refused (state=%d): the coefficients were modified, the tree is no longer one transform" % self.state)
         n = len(b)
         d, i = (C.c_int * n)(*[v[0] for v in b]), (C.c_int * n)(*[v[1] for v in b])
-        if self._L.pdwt_wpt_set_basis(self._h, d, i, n) != 0:
+        if self._fn("set_basis")(self._h, d, i, n) != 0:
             raise RuntimeError("set_basis failed (state=%d)" % self.state)
 
     # -- thresholds, norms, statistics over the basis --------------------------------------
     def soft_threshold(self, beta, do_thresh_appcoeffs=0):
         """In place on the nodes of the current basis; the all-``a`` node only when ``do_thresh_appcoeffs``."""
         self._need_coeffs("soft_threshold")
-        self._L.pdwt_wpt_soft_threshold(self._h, self._ct(beta), int(do_thresh_appcoeffs))
+        self._fn("soft_threshold")(self._h, self._ct(beta), int(do_thresh_appcoeffs))
 
     def hard_threshold(self, beta, do_thresh_appcoeffs=0):
         self._need_coeffs("hard_threshold")
-        self._L.pdwt_wpt_hard_threshold(self._h, self._ct(beta), int(do_thresh_appcoeffs))
+        self._fn("hard_threshold")(self._h, self._ct(beta), int(do_thresh_appcoeffs))
 
     def norm1(self):
         """Sum of |c| over the nodes of the basis, in double."""
-        v = float(self._L.pdwt_wpt_norm1(self._h))
+        v = float(self._fn("norm1")(self._h))
         if v < 0:
             raise RuntimeError("norm1 refused (state=%d): the coefficients are not valid" % self.state)
         return v
 
     def node_stats(self, depth):
-        """{sum_abs, sum_sq, max_abs: float64 arrays of 4^depth} of the nodes of ``depth``, one batched launch."""
-        n = 4 ** int(depth)
+        """{sum_abs, sum_sq, max_abs: float64 arrays of 4^depth (1-D: 2^depth, over all rows)} of the nodes of ``depth``, one batched launch."""
+        n = self._arity ** int(depth)
         self.node_shape(depth)
         out = (N.BandStats * n)()
-        if self._L.pdwt_wpt_node_stats(self._h, int(depth), out) != 0:
+        if self._fn("node_stats")(self._h, int(depth), out) != 0:
             raise RuntimeError("node_stats refused (state=%d): the coefficients are not valid" % self.state)
         a = np.frombuffer(out, dtype=np.float64).reshape(n, 5)
         return {"sum_abs": a[:, 1].copy(), "sum_sq": a[:, 2].copy(), "max_abs": a[:, 3].copy()}
 
     def estimate_sigma(self):
-        """Noise level from the finest diagonal node: median |node "d"| / 0.6744897501960817."""
-        s = float(self._L.pdwt_wpt_estimate_sigma(self._h))
+        """Noise level from the finest diagonal (1-D: detail) node: median |node "d"| / 0.6744897501960817 (1-D: over the whole batch)."""
+        s = float(self._fn("estimate_sigma")(self._h))
         if s < 0:
             raise RuntimeError("estimate_sigma refused (state=%d): the coefficients are not valid" % self.state)
         return s
@@ -291,97 +299,20 @@ class PitchedDeviceArray(DeviceArray):
         return out
 
 
-class WaveletPackets1D:
+class WaveletPackets1D(WaveletPackets2D):
     """WaveletPackets1D(rows, wname, levels, dtype=None): the packet tree of every row of a 2-D batch ``(Nr, Nc)`` -- a numpy array or a
     contiguous float32 / float64 device tensor (copied device to device) -- ``pywt.WaveletPacket(mode='periodization')`` per row.  Depth
     ``l`` is stored as ``(Nr, 2^l, n_l)``; one basis serves the whole batch.  Same methods and state machine as ``WaveletPackets2D``;
-    paths are over ``ad``.  Device memory about (levels + 1) batches.  ``fused``: the whole tree of a row runs in one launch."""
+    paths are over ``ad``; ``node_shape(depth)`` is ``(Nr, n_depth)``.  Device memory about (levels + 1) batches.  ``fused``: the whole
+    tree of a row runs in one launch.  Only what the rows change is written here."""
 
-    def __init__(self, rows, wname, levels, dtype=None):
-        N.require_gpu()
-        dev = _device_source(rows)
-        if dev is not None:
-            ptr, shape, dt = dev
-            if dtype is not None and np.dtype(dtype) != dt:
-                raise TypeError("dtype does not match the device tensor")
-            _sync_producer()
-            src, on_host, keep = C.c_void_p(ptr), 0, None
-        else:
-            rows = np.asarray(rows)
-            dt = np.dtype(dtype or (rows.dtype if rows.dtype in (np.float32, np.float64) else np.float32))
-            keep = np.ascontiguousarray(rows, dtype=dt)
-            shape, src, on_host = keep.shape, keep.ctypes.data_as(C.c_void_p), 1
-        if len(shape) != 2:
-            raise ValueError("WaveletPackets1D needs a 2-D batch of rows (Nr, Nc)")
-        self.dtype, self.shape, self.wname = np.dtype(dt), tuple(int(v) for v in shape), wname
-        self._L = N.host(self.dtype)
-        self._ct = C.c_float if self.dtype == np.float32 else C.c_double
-        self._h = self._L.pdwt_wp1h_new(src, self.shape[0], self.shape[1], wname.encode(), int(levels), on_host)
-        del keep
-        if not self._h:
-            raise MemoryError("WaveletPackets1D allocation failed")
-
-    def close(self):
-        if getattr(self, "_h", None):
-            self._L.pdwt_wp1h_delete(self._h)
-        self._h = None
-
-    __del__ = close
-
-    # -- introspection ---------------------------------------------------------------------
-    @property
-    def info(self):
-        i = N.InfoWPT1()
-        self._L.pdwt_wp1h_info(self._h, C.byref(i))
-        return i
-
-    @property
-    def levels(self):
-        return self.info.nlevels
-
-    @property
-    def state(self):
-        return self._L.pdwt_wp1h_state(self._h)
+    _hpfx, _arity, _info_t = "pdwt_wp1h_", 2, N.InfoWPT1
+    _err_shape = "WaveletPackets1D needs a 2-D batch of rows (Nr, Nc)"
+    _err_alloc = "WaveletPackets1D allocation failed"
 
     @property
     def fused(self):
-        return bool(self._L.pdwt_wp1h_fused(self._h))
-
-    def node_shape(self, depth):
-        """(Nr, n_depth)"""
-        r, c = C.c_int(), C.c_int()
-        if self._L.pdwt_wp1h_node_shape(self._h, int(depth), C.byref(r), C.byref(c)) <= 0:
-            raise IndexError(depth)
-        return r.value, c.value
-
-    def _node(self, node):
-        d, i = path_to_index(node, 2) if isinstance(node, str) else (int(node[0]), int(node[1]))
-        if not (0 <= d <= self.levels and 0 <= i < 2 ** d):
-            raise IndexError(node)
-        return d, i
-
-    def _need_coeffs(self, what):
-        if self.state in (W_INVERSE, W_CREATION_ERROR):
-            raise RuntimeError("%s refused (state=%d): the coefficients are not valid" % (what, self.state))
-
-    # -- transforms ------------------------------------------------------------------------
-    def forward(self):
-        self._L.pdwt_wp1h_forward(self._h)
-
-    def inverse(self):
-        self._L.pdwt_wp1h_inverse(self._h)
-
-    # -- data in and out -------------------------------------------------------------------
-    def get_image(self):
-        out = np.empty(self.shape, dtype=self.dtype)
-        if self._L.pdwt_wp1h_get_image(self._h, out.ctypes.data_as(C.c_void_p)) != out.size:
-            raise RuntimeError("get_image failed")
-        return out
-
-    _upload = WaveletPackets2D._upload
-
-    def set_image(self, rows):
-        self._upload(self._L.pdwt_wp1h_set_image, rows, self.shape[0] * self.shape[1])
+        return bool(self._fn("fused")(self._h))
 
     def get_level(self, depth, order="natural"):
         """All nodes of ``depth`` as one array of shape (Nr, 2^depth, n_depth); ``order="freq"``: the nodes in frequency order."""
@@ -390,38 +321,20 @@ class WaveletPackets1D:
         self._need_coeffs("get_level")
         r, n = self.node_shape(depth)
         out = np.empty((r, 2 ** int(depth), n), dtype=self.dtype)
-        if self._L.pdwt_wp1h_get_level(self._h, out.ctypes.data_as(C.c_void_p), int(depth)) != out.size:
+        if self._fn("get_level")(self._h, out.ctypes.data_as(C.c_void_p), int(depth)) != out.size:
             raise RuntimeError("get_level(%d) failed (state=%d)" % (depth, self.state))
         return out if order == "natural" else np.ascontiguousarray(out[:, frequency_order(depth)])
-
-    def get_node(self, node):
-        self._need_coeffs("get_node")
-        d, i = self._node(node)
-        out = np.empty(self.node_shape(d), dtype=self.dtype)
-        if self._L.pdwt_wp1h_get_node(self._h, out.ctypes.data_as(C.c_void_p), d, i) != out.size:
-            raise RuntimeError("get_node(%r) failed (state=%d)" % (node, self.state))
-        return out
-
-    def set_node(self, node, arr):
-        """Overwrite one node with a dense (Nr, n) numpy array or device tensor; the state becomes W_THRESHOLD.  Needs the tree of a
-        ``forward()``: refused (``RuntimeError``) before it and after ``inverse()``."""
-        if self.state not in (W_FORWARD, W_THRESHOLD):
-            raise RuntimeError("set_node refused (state=%d): run forward() first" % self.state)
-        d, i = self._node(node)
-        r, c = self.node_shape(d)
-        if self._upload(self._L.pdwt_wp1h_set_node, arr, r * c, d, i) != r * c:
-            raise RuntimeError("set_node(%r) failed (state=%d)" % (node, self.state))
 
     def node_int_ptr(self, node):
         """Device address of row 0 of the node; see ``node_pitch``."""
         d, i = self._node(node)
-        return self._L.pdwt_wp1h_node_int_ptr(self._h, d, i, None)
+        return self._fn("node_int_ptr")(self._h, d, i, None)
 
     def node_pitch(self, node):
         """Distance between consecutive rows of the node, in elements: 2^depth * n_depth."""
         d, i = self._node(node)
         p = C.c_longlong()
-        self._L.pdwt_wp1h_node_int_ptr(self._h, d, i, C.byref(p))
+        self._fn("node_int_ptr")(self._h, d, i, C.byref(p))
         return p.value
 
     def node_view(self, node):
@@ -429,10 +342,6 @@ class WaveletPackets1D:
         d, _ = self._node(node)
         return PitchedDeviceArray(self, self.node_int_ptr(node), self.node_shape(d), self.dtype, self.node_pitch(node))
 
-    def sync(self):
-        return N.hip().pdwt_sync()
-
-    # -- costs and bases -------------------------------------------------------------------
     def node_costs(self, cost="shannon", per_row=False):
         """[float64 array of 2^depth costs for depth 0 .. levels], summed over the rows in row order; ``"l1"``: sum |c|, ``"shannon"``:
         -sum c^2 ln c^2.  ``per_row=True``: arrays of shape (Nr, 2^depth) instead, what a basis per row would be chosen from.  One
@@ -443,69 +352,7 @@ class WaveletPackets1D:
         for d in range(self.levels + 1):
             c = np.empty(2 ** d, dtype=np.float64)
             pr = np.empty((self.shape[0], 2 ** d), dtype=np.float64)
-            if self._L.pdwt_wp1h_node_costs(self._h, d, COSTS[cost], c.ctypes.data_as(C.POINTER(C.c_double)), pr.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+            if self._fn("node_costs")(self._h, d, COSTS[cost], c.ctypes.data_as(C.POINTER(C.c_double)), pr.ctypes.data_as(C.POINTER(C.c_double))) != 0:
                 raise RuntimeError("node_costs refused (state=%d): the coefficients are not valid" % self.state)
             out.append(pr if per_row else c)
         return out
-
-    @property
-    def basis(self):
-        """The current basis as a sorted list of (depth, idx)."""
-        n = self._L.pdwt_wp1h_basis_size(self._h)
-        d, i = (C.c_int * max(n, 1))(), (C.c_int * max(n, 1))()
-        self._L.pdwt_wp1h_get_basis(self._h, d, i)
-        return [(d[k], i[k]) for k in range(n)]
-
-    def best_basis(self, cost="shannon"):
-        """Coifman-Wickerhauser search, bottom-up on the host over ``node_costs(cost)`` (summed over the rows): a parent is kept when
-        its cost is <= the sum of its two children's best costs.  Installs the basis and returns it.  Needs the untouched tree of one
-        forward()."""
-        if cost not in COSTS:
-            raise ValueError("cost must be 'l1' or 'shannon'")
-        if self._L.pdwt_wp1h_best_basis(self._h, COSTS[cost]) < 1:
-            raise RuntimeError("best_basis refused (state=%d): it needs the coefficients of forward(), unmodified" % self.state)
-        return self.basis
-
-    def set_basis(self, nodes):
-        """Install a basis: paths or (depth, idx) pairs that partition the tree (``ValueError`` otherwise)."""
-        b = check_basis(nodes, self.levels, 2)
-        if self.state == W_THRESHOLD:
-            raise RuntimeError("set_basis refused (state=%d): the coefficients were modified, the tree is no longer one transform" % self.state)
-        n = len(b)
-        d, i = (C.c_int * n)(*[v[0] for v in b]), (C.c_int * n)(*[v[1] for v in b])
-        if self._L.pdwt_wp1h_set_basis(self._h, d, i, n) != 0:
-            raise RuntimeError("set_basis failed (state=%d)" % self.state)
-
-    # -- thresholds, norms, statistics over the basis --------------------------------------
-    def soft_threshold(self, beta, do_thresh_appcoeffs=0):
-        """In place on the nodes of the current basis; the all-``a`` node only when ``do_thresh_appcoeffs``."""
-        self._need_coeffs("soft_threshold")
-        self._L.pdwt_wp1h_soft_threshold(self._h, self._ct(beta), int(do_thresh_appcoeffs))
-
-    def hard_threshold(self, beta, do_thresh_appcoeffs=0):
-        self._need_coeffs("hard_threshold")
-        self._L.pdwt_wp1h_hard_threshold(self._h, self._ct(beta), int(do_thresh_appcoeffs))
-
-    def norm1(self):
-        """Sum of |c| over the nodes of the basis, in double."""
-        v = float(self._L.pdwt_wp1h_norm1(self._h))
-        if v < 0:
-            raise RuntimeError("norm1 refused (state=%d): the coefficients are not valid" % self.state)
-        return v
-
-    def node_stats(self, depth):
-        """{sum_abs, sum_sq, max_abs: float64 arrays of 2^depth} of the nodes of ``depth`` over all rows, one launch."""
-        n = 2 ** int(depth)
-        self.node_shape(depth)
-        out = (N.BandStats * n)()
-        if self._L.pdwt_wp1h_node_stats(self._h, int(depth), out) != 0:
-            raise RuntimeError("node_stats refused (state=%d): the coefficients are not valid" % self.state)
-        a = np.frombuffer(out, dtype=np.float64).reshape(n, 5)
-        return {"sum_abs": a[:, 1].copy(), "sum_sq": a[:, 2].copy(), "max_abs": a[:, 3].copy()}
-
-    def estimate_sigma(self):
-        """Noise level from the finest detail node: median |node "d"| / 0.6744897501960817 over the whole batch."""
-        s = float(self._L.pdwt_wp1h_estimate_sigma(self._h))
-        if s < 0:
-            raise RuntimeError("estimate_sigma refused (state=%d): the coefficients are not valid" % self.state)
-        return s
