@@ -556,6 +556,42 @@ int pdwt_ext1d_inverse_f32(float* d_dst, float* const* d_coeffs, int nr, int nc,
 int pdwt_ext1d_inverse_f64(double* d_dst, double* const* d_coeffs, int nr, int nc, int levels, const pdwt_filters_f64* f, double* d_tmp);
 
 /* ---------------------------------------------------------------------------------------------
+ * Batched 2-D DWT with boundary modes (pdwt_amd/csrc/dwt_ext2db.hip; the class: BoundaryWaveletsImages, include/wt_ext.h): the
+ * transform of "2-D DWT with boundary modes" on every image of a B x Nr x Nc stack -- pywt.wavedec2(x, w, mode, level,
+ * axes=(-2, -1)).  Band table of `levels` levels (1 .. 32): [A_L, H1, V1, D1, ..., H_L, V_L, D_L], level 1 the finest; band num of
+ * the batch is ONE contiguous B x nr_l x nc_l stack, image-major (band num of image b starts b * nr_l * nc_l elements in).  The
+ * per-image shapes are those of pdwt_ext_band_shape.
+ *
+ * Every entry takes 1 <= B <= 65535, an even f->hlen of 2 .. 40 (Haar: the bank's own taps), nr and nc >= hlen - 1 at every level it
+ * runs, nr * nc < 2^31, at most 65535 rows of tiles and a mode 0 .. 4; anything else, or a NULL pointer, is PDWT_EINVAL and nothing is
+ * launched.  Offsets into the stacks are computed in size_t.  Buffers need only be aligned to their element type.  Asynchronous on the
+ * library stream.
+ *
+ * The level entries run ONE level of all B images in one launch (the x-y tile kernels of the 3-D transform, the images as planes):
+ * forward reads d_src (B x nr x nc) and writes the four stacks (B x N_r x N_c each); inverse reads them and writes d_dst.
+ * The whole-transform entries take d_coeffs, a HOST table of 3 * levels + 1 device pointers in the band order above.  When the
+ * pyramid of one image fits the LDS of a workgroup (pdwt_ext2db_fused: 1 / 0; LDS bytes: forward (Nr Nc + 2 Nr N_c1) elements plus
+ * two index tables, inverse 2 N_r1 N_c1 + 2 Nr N_c1 elements, the larger within 160 KiB: float32 up to about 140 x 140, float64 about
+ * 100 x 100 with a short bank) ALL levels of an image run in one workgroup and a transform is ONE launch, whatever levels and B: the
+ * batch is read once, every band written once, and d_tmp is not used (may be NULL).  Otherwise they loop the level entries, keeping
+ * the intermediate approximations in d_tmp, which must hold pdwt_ext2db_tmp_elems elements (2 * B * N_r1 * N_c1; 0 exactly when
+ * fused).  They return PDWT_EXT2DB_FUSED or PDWT_EXT2DB_LEVELS to tell which path ran, or a negative error.  Both paths, and the 2-D
+ * level entries applied image by image, give the same bits.  forward leaves d_src intact, inverse leaves the bands intact.
+ * ------------------------------------------------------------------------------------------- */
+#define PDWT_EXT2DB_LEVELS 0 /* the per-level kernels ran */
+#define PDWT_EXT2DB_FUSED 1  /* one launch ran all levels */
+int pdwt_ext2db_fused(int Nr, int Nc, int hlen, int levels, int elem_size);                      /* elem_size 4 or 8 */
+long long pdwt_ext2db_tmp_elems(int B, int Nr, int Nc, int hlen, int levels, int elem_size);
+int pdwt_ext2db_forward_level_f32(const float* d_src, float* d_a, float* d_h, float* d_v, float* d_d, int B, int nr, int nc, int mode, const pdwt_filters_f32* f);
+int pdwt_ext2db_forward_level_f64(const double* d_src, double* d_a, double* d_h, double* d_v, double* d_d, int B, int nr, int nc, int mode, const pdwt_filters_f64* f);
+int pdwt_ext2db_inverse_level_f32(float* d_dst, const float* d_a, const float* d_h, const float* d_v, const float* d_d, int B, int nr, int nc, const pdwt_filters_f32* f);
+int pdwt_ext2db_inverse_level_f64(double* d_dst, const double* d_a, const double* d_h, const double* d_v, const double* d_d, int B, int nr, int nc, const pdwt_filters_f64* f);
+int pdwt_ext2db_forward_f32(const float* d_src, float* const* d_coeffs, int B, int Nr, int Nc, int levels, int mode, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext2db_forward_f64(const double* d_src, double* const* d_coeffs, int B, int Nr, int Nc, int levels, int mode, const pdwt_filters_f64* f, double* d_tmp);
+int pdwt_ext2db_inverse_f32(float* d_dst, float* const* d_coeffs, int B, int Nr, int Nc, int levels, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext2db_inverse_f64(double* d_dst, double* const* d_coeffs, int B, int Nr, int Nc, int levels, const pdwt_filters_f64* f, double* d_tmp);
+
+/* ---------------------------------------------------------------------------------------------
  * 3-D DWT with boundary modes (pdwt_amd/csrc/dwt_ext3d.hip; the class: BoundaryWavelets3D, include/wt_ext.h): the mathematics of
  * "2-D DWT with boundary modes" along x (the last axis), then y, then z of an nz x nr x nc volume -- pywt.wavedecn(vol, w, mode,
  * level).  One level gives eight bands of ((nz + F - 1) / 2) x ((nr + F - 1) / 2) x ((nc + F - 1) / 2), row-major; the modes are the

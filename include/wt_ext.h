@@ -4,7 +4,7 @@
  * libpdwtd.so), every device action a C-ABI call into libpdwt_hip.so (include/pdwt_hip.h "2-D DWT with boundary modes"; kernels:
  * pdwt_amd/csrc/dwt_ext.hip).
  * `BoundaryWavelets1D`, further down, is the same transform along the last axis of a batch of rows; `BoundaryWavelets3D`, below
- * it, along the three axes of a volume.
+ * it, along the three axes of a volume; `BoundaryWaveletsImages`, at the end, the 2-D transform of every image of a batch.
  *
  * Modes (PyWavelets' names and semantics): 0 zero, 1 constant, 2 symmetric (PyWavelets' default), 3 reflect, 4 periodic.  The
  * transform is pywt.wavedec2 of those modes: a level takes an nr x nc approximation to four bands of ((nr + hlen - 1) / 2) x
@@ -36,7 +36,7 @@ struct w_info_bw {
     int mode;
 };
 
-/* What the three classes of this header share: every member but `winfos`, and every method whose signature does not name the number of
+/* What the four classes of this header share: every member but `winfos`, and every method whose signature does not name the number of
  * axes.  Written once in pdwt_amd/csrc/wt_ext.cpp; what differs between the classes is one `bw_ops` table each.  Not for direct use. */
 struct bw_ops;
 class BoundaryTransform {
@@ -72,11 +72,11 @@ class BoundaryTransform {
   protected:
     BoundaryTransform();
     ~BoundaryTransform();
-    /* the constructor of all three: dims = {Nz, Nr, Nc} (1 for an axis the class does not have); *nlevels holds the levels asked for and
+    /* the constructor of all four: dims = {Nz, Nr, Nc} (1 for an axis the class does not have; the images of a batch are Nz); *nlevels holds the levels asked for and
      * gets the clamped ones, *hlen the length of the bank, as far as the construction came */
     void create(const bw_ops& ops, DTYPE* src, const int* dims, const char* wname, int mode, int memisonhost, int* nlevels, int* hlen);
     long long band_shape(int num, int* shape) const; /* elements of band num and its {nz, nr, nc}; 0 for a bad index */
-    const bw_ops* ops_;                              /* which of the three transforms this is */
+    const bw_ops* ops_;                              /* which of the four transforms this is */
     void* priv_;                                     /* bank, device, geometry, the band allocation, the scratch */
 
   private:
@@ -162,6 +162,54 @@ class BoundaryWavelets3D : public BoundaryTransform {
     static int geometry(int Nz, int Nr, int Nc, int hlen, int levels, int* nz, int* nr, int* nc);
 
     long long coeff_shape(int num, int* nz, int* nr, int* nc) const; /* elements of band num, 0 for a bad index */
+};
+
+/*
+ * `BoundaryWaveletsImages`: the 2-D transform of the first class on every image of a B x Nr x Nc batch -- pywt.wavedec2(x, wname, mode,
+ * levels, axes=(-2, -1)) (include/pdwt_hip.h "Batched 2-D DWT with boundary modes"; kernels: pdwt_amd/csrc/dwt_ext2db.hip).  Definitions,
+ * band order, orientation and level clamp are those of BoundaryWavelets; member for member that class, with these differences:
+ * Bands.  Band num is ONE contiguous B x nr_l x nc_l stack, image-major: band num of image b is d_coeffs[num] + b * nr_l * nc_l.
+ * get_coeff / set_coeff move a whole stack, get_image / set_image the whole batch.  1 <= B <= 65535, Nr * Nc < 2^31.
+ * One launch.  When the pyramid of one image fits the LDS of a workgroup (fused() == 1: float32 up to about 140 x 140) forward() and
+ * inverse() are ONE kernel launch each, whatever the number of levels and images: one workgroup per image, the batch read once, every
+ * band written once.  Larger images run one launch per level through two scratch stacks of level-1 size, which only such an
+ * instance allocates.  Both paths, and a loop over B BoundaryWavelets instances, give the same bits.
+ * Statistics, two sets.
+ *   POOLED (the inherited methods: band_stats, all_band_stats, estimate_sigma, threshold_bands, denoise, norm1, soft_threshold,
+ *   hard_threshold): a band is the whole stack, as BoundaryWavelets1D pools its rows.  The finest diagonal band is the D1 stack
+ *   (band 3) of all images together; N of the universal threshold is Nr * Nc (one image).
+ *   PER IMAGE (the images_* methods below, the semantics of WaveletsImages, include/wt_batch.h): arrays are image-major with
+ *   B * num_bands() entries, entry [b * num_bands() + k] = band k of image b.  Every call is a fixed number of launches and one copy to
+ *   the host whatever B (the pdwt_bandbatch_* entries over a device table of the B * num_bands() slice pointers, built on first use).
+ *   They return PDWT_OK, PDWT_EINVAL when refused (the coefficients of a forward() are needed, as for the pooled set; images_norm1
+ *   only needs them readable), or the code of the entry that failed.
+ */
+struct w_info_bwb {
+    int B, Nr, Nc;
+    int nlevels; /* after clamping */
+    int hlen;
+    int mode;
+};
+
+#define BWB_MAX_IMAGES 65535
+
+class BoundaryWaveletsImages : public BoundaryTransform {
+  public:
+    w_info_bwb winfos;
+
+    BoundaryWaveletsImages(DTYPE* imgs, int B, int Nr, int Nc, const char* wname, int levels, int mode, int memisonhost = 1);
+
+    /* elements of band num (the whole stack) and its shape B x nr x nc, 0 for a bad index */
+    long long coeff_shape(int num, int* b, int* nr, int* nc) const;
+    int fused() const; /* 1: forward() and inverse() of this instance are one launch each; 0 after W_CREATION_ERROR */
+
+    int images_all_band_stats(w_band_stats* out, int with_median = 0); /* out: B * num_bands() */
+    int images_estimate_sigma(double* sigma_out);                      /* B sigmas, each from its own D1 */
+    int images_threshold_bands(const DTYPE* betas, int kind = 0);      /* betas: B * num_bands(); a negative beta leaves that band alone */
+    /* sigma_in NULL or sigma_in[b] < 0: estimated from image b.  method 0 VisuShrink, 1 BayesShrink (the rule of wt.h, per image);
+     * sigma_out: B; betas_out (may be NULL): B * num_bands(), band 0 of every image -1 */
+    int images_denoise(int method, const double* sigma_in, int kind, double* sigma_out, DTYPE* betas_out = NULL);
+    int images_norm1(double* out); /* B sums |c| over the bands of each image, in double */
 };
 
 #endif

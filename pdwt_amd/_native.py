@@ -33,6 +33,11 @@ class InfoBW(C.Structure):
     _fields_ = [("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int), ("mode", C.c_int)]
 
 
+class InfoBWB(C.Structure):
+    """== w_info_bwb (include/wt_ext.h)."""
+    _fields_ = [("B", C.c_int), ("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int), ("mode", C.c_int)]
+
+
 class InfoBW3(C.Structure):
     """== w_info_bw3 (include/wt_ext.h)."""
     _fields_ = [("Nz", C.c_int), ("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int), ("mode", C.c_int)]
@@ -79,6 +84,7 @@ PLAIN_SYMBOLS = ["pdwt_device_count", "pdwt_set_device", "pdwt_get_device", "pdw
                  "pdwt_sum_scratch_doubles", "pdwt_sum_scratch_read", "pdwt_num_bands3d", "pdwt_band_size3d", "pdwt_tmp_elems3d",
                  "pdwt_num_bands_swt3d", "pdwt_band_size_swt3d", "pdwt_tmp_elems_swt3d", "pdwt_num_bands_ext", "pdwt_ext_band_shape",
                  "pdwt_num_bands_ext1d", "pdwt_ext1d_band_len", "pdwt_ext1d_fused", "pdwt_ext1d_tmp_elems",
+                 "pdwt_ext2db_fused", "pdwt_ext2db_tmp_elems",
                  "pdwt_num_bands_ext3d", "pdwt_ext3d_band_shape", "pdwt_ext3d_tmp_elems", "pdwt_ext3d_tmp_approx_offset",
                  "pdwt_wp1_geometry", "pdwt_wp1_fused", "pdwt_wp1_tmp_elems", "pdwt_wp1_frequency_order", "pdwt_wp1_state_table", "pdwt_memcpy2d"]
 TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coeffs_buffer", "copy_coeffs_buffer",
@@ -91,6 +97,7 @@ TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coe
                   "wpt2d_forward_level", "wpt2d_inverse_level", "wpt2d_node_cost", "ext2d_forward_level", "ext2d_inverse_level",
                   "ext1d_forward_level", "ext1d_inverse_level", "ext1d_forward", "ext1d_inverse",
                   "ext3d_forward_level", "ext3d_inverse_level",
+                  "ext2db_forward_level", "ext2db_inverse_level", "ext2db_forward", "ext2db_inverse",
                   "wp1_forward_level", "wp1_inverse_level", "wp1_forward", "wp1_inverse", "wp1_moments", "wp1_thresh"] + DRIVERS + HAAR_DRIVERS)
 
 _hip = None
@@ -236,6 +243,12 @@ def hip():
         # volumes with boundary modes, one level: (volume, HOST table of the 8 band pointers aaa .. ddd, nz, nr, nc, [mode,] bank, scratch)
         getattr(L, "pdwt_ext3d_forward_level_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, C.POINTER(FT), vp]
         getattr(L, "pdwt_ext3d_inverse_level_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, C.POINTER(FT), vp]
+        # batched 2-D with boundary modes: one level of B images (src, A, H, V, D stacks, B, nr, nc, [mode,] bank); all levels (src or dst,
+        # HOST table of 3 * levels + 1 device pointers, B, Nr, Nc, levels, [mode,] bank, scratch or NULL) -> 1 fused / 0 per level / < 0
+        getattr(L, "pdwt_ext2db_forward_level_" + sfx).argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, C.POINTER(FT)]
+        getattr(L, "pdwt_ext2db_inverse_level_" + sfx).argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, C.POINTER(FT)]
+        getattr(L, "pdwt_ext2db_forward_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, ci, C.POINTER(FT), vp]
+        getattr(L, "pdwt_ext2db_inverse_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, C.POINTER(FT), vp]
         # batched 1-D wavelet packets: one depth step (parents, children, nr, nnodes, n, [device list or NULL, count,] bank); the whole
         # tree (src or dst, HOST table of `levels` device pointers, nr, nc, levels, [device state table,] bank) -> 1 fused / 0 per level / < 0
         getattr(L, "pdwt_wp1_forward_level_" + sfx).argtypes = [vp, vp, ci, ci, ci, C.POINTER(FT)]
@@ -264,6 +277,9 @@ def hip():
     L.pdwt_ext1d_fused.argtypes = [ci, ci, ci, ci]
     L.pdwt_ext1d_tmp_elems.restype = C.c_longlong
     L.pdwt_ext1d_tmp_elems.argtypes = [ci, ci, ci, ci, ci]
+    L.pdwt_ext2db_fused.argtypes = [ci, ci, ci, ci, ci]
+    L.pdwt_ext2db_tmp_elems.restype = C.c_longlong
+    L.pdwt_ext2db_tmp_elems.argtypes = [ci, ci, ci, ci, ci, ci]
     _hip = L
     return L
 
@@ -357,7 +373,7 @@ def host(dtype):
             getattr(L, pfx + "coeff_int_ptr").restype = C.c_ssize_t
             getattr(L, pfx + "coeff_int_ptr").argtypes = [vp, ci]
         # band statistics and noise-adaptive thresholds: the same five handle functions on the four classes
-        for pfx in ("pdwt_wavelets_", "pdwt_wavelets3d_", "pdwt_swt3d_", "pdwt_bw_", "pdwt_bw1_", "pdwt_bw3_"):
+        for pfx in ("pdwt_wavelets_", "pdwt_wavelets3d_", "pdwt_swt3d_", "pdwt_bw_", "pdwt_bw1_", "pdwt_bw3_", "pdwt_bwb_"):
             getattr(L, pfx + "band_stats").argtypes = [vp, ci, C.POINTER(BandStats), ci]
             getattr(L, pfx + "all_band_stats").argtypes = [vp, C.POINTER(BandStats), ci]
             getattr(L, pfx + "estimate_sigma").restype = C.c_double
@@ -489,6 +505,33 @@ def host(dtype):
             getattr(L, "pdwt_bw3_" + n).argtypes = [vp, ct, ci]
         L.pdwt_bw3_norm1.restype = C.c_double
         L.pdwt_bw3_norm1.argtypes = [vp]
+        # BoundaryWaveletsImages: the handle API of the three above, and the per-image statistics (the signatures of pdwt_images_*)
+        L.pdwt_bwb_new.restype = vp
+        L.pdwt_bwb_new.argtypes = [vp, ci, ci, ci, C.c_char_p, ci, ci, ci]
+        for n in ("delete", "forward", "inverse", "state", "num_bands", "fused"):
+            getattr(L, "pdwt_bwb_" + n).argtypes = [vp]
+        L.pdwt_bwb_get_image.argtypes = [vp, vp]
+        L.pdwt_bwb_set_image.argtypes = [vp, vp, ci]
+        L.pdwt_bwb_info.argtypes = [vp, C.POINTER(InfoBWB)]
+        L.pdwt_bwb_geometry.argtypes = [ci, ci, ci, ci, pi, pi]
+        L.pdwt_bwb_mode_index.argtypes = [C.c_char_p]
+        L.pdwt_bwb_coeff_shape.restype = C.c_longlong
+        L.pdwt_bwb_coeff_shape.argtypes = [vp, ci, pi, pi, pi]
+        L.pdwt_bwb_get_coeff.argtypes = [vp, vp, ci]
+        L.pdwt_bwb_set_coeff.argtypes = [vp, vp, ci, ci]
+        L.pdwt_bwb_image_int_ptr.restype = C.c_ssize_t
+        L.pdwt_bwb_image_int_ptr.argtypes = [vp]
+        L.pdwt_bwb_coeff_int_ptr.restype = C.c_ssize_t
+        L.pdwt_bwb_coeff_int_ptr.argtypes = [vp, ci]
+        for n in ("soft_threshold", "hard_threshold"):
+            getattr(L, "pdwt_bwb_" + n).argtypes = [vp, ct, ci]
+        L.pdwt_bwb_norm1.restype = C.c_double
+        L.pdwt_bwb_norm1.argtypes = [vp]
+        L.pdwt_bwb_images_all_band_stats.argtypes = [vp, C.POINTER(BandStats), ci]
+        L.pdwt_bwb_images_estimate_sigma.argtypes = [vp, C.POINTER(C.c_double)]
+        L.pdwt_bwb_images_threshold_bands.argtypes = [vp, vp, ci]
+        L.pdwt_bwb_images_denoise.argtypes = [vp, ci, C.POINTER(C.c_double), ci, C.POINTER(C.c_double), vp]
+        L.pdwt_bwb_images_norm1.argtypes = [vp, C.POINTER(C.c_double)]
         _host[dt] = L
     return _host[dt]
 

@@ -8,6 +8,10 @@ levels, axis=-1)``, bands ``[A_L, D_1, ..., D_L]``, all levels in one kernel lau
 
 ``BoundaryWavelets3D`` (C++ ``BoundaryWavelets3D``) is the same along the three axes of a volume: ``pywt.wavedecn(vol, wname, mode,
 levels)``, bands in the order of ``Wavelets3D``.
+
+``BoundaryImageBatch`` (C++ ``BoundaryWaveletsImages``) is the 2-D transform of every image of a ``(B, Nr, Nc)`` batch:
+``pywt.wavedec2(x, wname, mode, levels, axes=(-2, -1))``, the whole pyramid of an image in one workgroup when it fits LDS, and the
+per-image statistics and denoising of ``ImageBatch``.
 """
 import ctypes as C
 
@@ -259,4 +263,127 @@ class BoundaryWavelets3D(BoundaryWavelets2D):
         out = np.empty(self.coeff_shape(num), dtype=self.dtype)
         if self._bs("get_coeff")(self._h, out.ctypes.data_as(C.c_void_p), int(num)) != min(out.size, 2**31 - 1):
             raise RuntimeError("get_coeff(%d) failed (state=%d)" % (num, self.state))
+        return out
+
+
+class BoundaryImageBatch(BoundaryWavelets2D):
+    """BoundaryImageBatch(imgs, wname, levels, mode="symmetric", dtype=None): the 2-D DWT with boundary modes of ``B`` equally sized
+    images.  ``imgs`` is a 3-D ``(B, Nr, Nc)`` numpy array or a contiguous float32 / float64 device tensor; every image is transformed as
+    ``BoundaryWavelets2D`` transforms it (the same bits), bands ``[A_L, H1, V1, D1, ..., H_L, V_L, D_L]``; band ``num`` of the batch is
+    one ``(B, nr_l, nc_l)`` stack, which is what ``get_coeff`` / ``set_coeff`` / ``coeff_view`` move.  1 <= B <= 65535.  When the pyramid
+    of one image fits the LDS of a workgroup (``fused``) ``forward()`` and ``inverse()`` are one kernel launch each, whatever ``levels``
+    and ``B``.  Same state machine as ``BoundaryWavelets2D``.
+
+    Statistics.  ``all_band_stats``, ``estimate_sigma``, ``threshold_bands``, ``denoise`` and ``norm1`` carry the names, signatures and
+    PER-IMAGE meaning of ``ImageBatch`` (arrays ``(B, nbands)`` / ``(B,)``, every image its own sigma).  The pooled ones of the base
+    class, in which a band is the whole stack (the finest diagonal band = the D1 stack of all images, N of the universal threshold =
+    Nr * Nc), are ``band_stats`` and ``pooled_all_band_stats`` / ``pooled_estimate_sigma`` / ``pooled_threshold_bands`` /
+    ``pooled_denoise`` / ``pooled_norm1``; ``soft_threshold`` / ``hard_threshold`` apply one beta to every image."""
+
+    _hpfx = "pdwt_bwb_"
+    _info_t = N.InfoBWB
+
+    @staticmethod
+    def _shape2(shape):
+        if len(shape) != 3:
+            raise ValueError("BoundaryImageBatch needs a batch of images (B, Nr, Nc)")
+        return shape
+
+    def __len__(self):
+        return self.shape[0]
+
+    def coeff_shape(self, num):
+        b, r, c = C.c_int(), C.c_int(), C.c_int()
+        if self._bs("coeff_shape")(self._h, int(num), C.byref(b), C.byref(r), C.byref(c)) <= 0:
+            raise IndexError(num)
+        return b.value, r.value, c.value
+
+    band_shape = coeff_shape
+
+    @property
+    def fused(self):
+        """True when ``forward()`` and ``inverse()`` of this instance are one kernel launch each (one workgroup per image, all levels
+        in LDS); False: one launch per level over the stacks."""
+        return bool(self._bs("fused")(self._h))
+
+    get_images = BoundaryWavelets2D.get_image
+
+    # -- the pooled statistics of the base class under their own names -------------------------
+    pooled_all_band_stats = BoundaryWavelets2D.all_band_stats
+    pooled_estimate_sigma = BoundaryWavelets2D.estimate_sigma
+    pooled_threshold_bands = BoundaryWavelets2D.threshold_bands
+    pooled_denoise = BoundaryWavelets2D.denoise
+    pooled_norm1 = BoundaryWavelets2D.norm1
+
+    # -- per image: the methods of ImageBatch ----------------------------------------------------
+    def _refused(self, what, rc=-1):
+        if rc != -1:  # (PDWT_EINVAL is the refusal; anything else is a device error: allocation, copy or launch)
+            return RuntimeError("%s failed on the device (code %d): %s" % (what, rc, (N.hip().pdwt_last_error_string() or b"").decode()))
+        return RuntimeError("%s refused (state=%d): the coefficients are not valid" % (what, self.state))
+
+    def all_band_stats(self, with_median=False):
+        """{n, sum_abs, sum_sq, max_abs, median_abs}: float64 arrays of shape (B, nbands), entry [b, k] = the statistics of band k of
+        image b (``median_abs`` NaN unless ``with_median``)."""
+        B, nb = self.shape[0], self.nbands
+        out = (N.BandStats * (B * max(nb, 1)))()
+        rc = self._bs("images_all_band_stats")(self._h, out, int(bool(with_median)))
+        if rc != 0:
+            raise self._refused("all_band_stats", rc)
+        a = np.frombuffer(out, dtype=np.float64).reshape(B, max(nb, 1), len(N.BandStats._fields_))[:, :nb]
+        return {k: a[:, :, i].copy() for i, (k, _) in enumerate(N.BandStats._fields_)}
+
+    def estimate_sigma(self):
+        """(B,) float64: every image's OWN noise level, median |its D1| / 0.6744897501960817."""
+        s = np.zeros(self.shape[0], dtype=np.float64)
+        rc = self._bs("images_estimate_sigma")(self._h, s.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != 0:
+            raise self._refused("estimate_sigma", rc)
+        return s
+
+    def threshold_bands(self, betas, kind="soft"):
+        """``betas``: (B, nbands), or (nbands,) for every image; a negative beta leaves that band of that image alone."""
+        if kind not in self.KINDS:
+            raise ValueError("kind must be 'soft' or 'hard'")
+        B, nb = self.shape[0], self.nbands
+        b = np.asarray(betas, dtype=self.dtype)
+        if b.shape == (nb,):
+            b = np.broadcast_to(b, (B, nb))
+        if b.shape != (B, nb):
+            raise ValueError("betas of shape %s for %d images of %d bands" % (b.shape, B, nb))
+        b = np.ascontiguousarray(b)
+        rc = self._bs("images_threshold_bands")(self._h, b.ctypes.data_as(C.c_void_p), self.KINDS[kind])
+        if rc != 0:
+            raise self._refused("threshold_bands", rc)
+
+    def denoise(self, method="bayes", sigma=None, kind="soft"):
+        """``BoundaryWavelets2D.denoise`` of every image, each with its own sigma: ``sigma`` None (estimated per image), a scalar or a
+        (B,) array.  Returns {"sigma": (B,) float64, "betas": (B, nbands) in the batch's dtype, betas[:, 0] == -1}."""
+        if method not in self.METHODS:
+            raise ValueError("method must be 'visu' or 'bayes'")
+        if kind not in self.KINDS:
+            raise ValueError("kind must be 'soft' or 'hard'")
+        B, nb = self.shape[0], self.nbands
+        sin = None
+        if sigma is not None:
+            sin = np.asarray(sigma, dtype=np.float64)
+            if sin.shape not in ((), (B,)):
+                raise ValueError("sigma must be None, a scalar or %d values" % B)
+            sin = np.ascontiguousarray(np.broadcast_to(sin, (B,)))
+            if not np.all(sin >= 0):
+                raise ValueError("sigma must be >= 0 (None: estimated)")
+        sout = np.zeros(B, dtype=np.float64)
+        betas = np.zeros((B, max(nb, 1)), dtype=self.dtype)
+        dp = C.POINTER(C.c_double)
+        rc = self._bs("images_denoise")(self._h, self.METHODS[method], sin.ctypes.data_as(dp) if sin is not None else None, self.KINDS[kind],
+                                        sout.ctypes.data_as(dp), betas.ctypes.data_as(C.c_void_p))
+        if rc != 0:
+            raise self._refused("denoise", rc)
+        return {"sigma": sout, "betas": betas[:, :nb]}
+
+    def norm1(self):
+        """(B,) float64: sum |c| over the bands of each image, accumulated in double (``pooled_norm1``: the sum over the batch)."""
+        out = np.zeros(self.shape[0], dtype=np.float64)
+        rc = self._bs("images_norm1")(self._h, out.ctypes.data_as(C.POINTER(C.c_double)))
+        if rc != 0:
+            raise self._refused("norm1", rc)
         return out

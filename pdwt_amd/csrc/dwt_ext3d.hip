@@ -10,23 +10,14 @@
 // element access: buffers need only be aligned to their element type.
 // Traffic per level and direction: one read of the input (plus the tile halos) and one write of the quadrants, then one read of the
 // quadrants and one write of the bands.
-#include "dwt_ext.hpp"
+#include "dwt_ext3d_xy.hpp"
 
 namespace pdwt {
 
-constexpr int kX3Threads = 256;
-constexpr int X3FX = 32, X3FY = 16;  // forward x-y tile (band positions): the tile of dwt_ext.hip
-constexpr int X3IX = 64, X3IY = 32;  // inverse x-y tile (parent samples, even starts)
+// (the x-y tile sizes and Ext3XYJob: dwt_ext3d_xy.hpp)
 constexpr int kX3ZThreads = 256;
 constexpr int X3ZC = 16;             // outputs per thread along z
 
-template <typename T>
-struct Ext3XYJob {
-    const T* src;    // forward: the level's input (nz, nr, nc)
-    T* dst;          // inverse: the level's output
-    T* q[4];         // quadrants (nz, hr, hc): A, H, V, D of dwt_ext.hpp = 2 * x band + y band
-    int nr, nc, hr, hc, mode;
-};
 template <typename T>
 struct Ext3ZJob {
     const T* src[4];   // forward: quadrants (nin planes); inverse: z-low bands (nin planes)
@@ -188,11 +179,14 @@ static int launch_ext3_z(bool fwd, const Ext3ZJob<T>& zj, const Taps2<T>& taps)
     return PDWT_OK;
 }
 
+// (external linkage: dwt_ext2db.hip runs the same instantiations on the images of a batch)
 template <typename T>
-static int run_ext3_xy(int hlen, bool fwd, const Ext3XYJob<T>& xy, int nz, const Taps2<T>& taps)
+int run_ext3_xy(int hlen, bool fwd, const Ext3XYJob<T>& xy, int nz, const Taps2<T>& taps)
 {
     return with_filter_length(hlen, [&](auto hl) { return launch_ext3_xy<T, decltype(hl)::value>(fwd, xy, nz, taps); });
 }
+template int run_ext3_xy<float>(int, bool, const Ext3XYJob<float>&, int, const Taps2<float>&);
+template int run_ext3_xy<double>(int, bool, const Ext3XYJob<double>&, int, const Taps2<double>&);
 template <typename T>
 static int run_ext3_z(int hlen, bool fwd, const Ext3ZJob<T>& zj, const Taps2<T>& taps)
 {

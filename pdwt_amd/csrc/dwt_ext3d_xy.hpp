@@ -1,0 +1,27 @@
+// dwt_ext3d_xy.hpp -- the x-y pass of dwt_ext3d.hip as other translation units see it: the tile sizes, the job and the launch.  The
+// kernels (k_ext3_fwd_xy / k_ext3_inv_xy: the tile stages of dwt_ext.hpp on plane blockIdx.z) are instantiated in dwt_ext3d.hip alone;
+// the batched 2-D transform (dwt_ext2db.hip) runs them with the planes = the images of a batch and the four quadrant pointers aimed at
+// its band stacks.
+#pragma once
+#include "dwt_ext.hpp"
+
+namespace pdwt {
+
+constexpr int kX3Threads = 256;
+constexpr int X3FX = 32, X3FY = 16;  // forward x-y tile (band positions): the tile of dwt_ext.hip
+constexpr int X3IX = 64, X3IY = 32;  // inverse x-y tile (parent samples, even starts)
+
+template <typename T>
+struct Ext3XYJob {
+    const T* src;    // forward: the level's input (nz, nr, nc)
+    T* dst;          // inverse: the level's output
+    T* q[4];         // quadrants (nz, hr, hc): A, H, V, D of dwt_ext.hpp = 2 * x band + y band
+    int nr, nc, hr, hc, mode;
+};
+
+// one launch over the nz planes: grid (tiles along x, tiles along y, nz).  The caller has checked the sizes (nz <= 65535, the rows of
+// tiles a grid dimension).  Defined and instantiated for float and double in dwt_ext3d.hip.
+template <typename T>
+int run_ext3_xy(int hlen, bool fwd, const Ext3XYJob<T>& xy, int nz, const Taps2<T>& taps);
+
+}  // namespace pdwt

@@ -1,6 +1,7 @@
-// wt_ext.cpp -- host side of the three boundary-mode classes of include/wt_ext.h, `BoundaryWavelets` (2-D), `BoundaryWavelets1D` (the
-// last axis of a batch of rows) and `BoundaryWavelets3D` (volumes), above the "... with boundary modes" entry points of
-// include/pdwt_hip.h, and their flat C handle APIs (pdwt_bw_*, pdwt_bw1_*, pdwt_bw3_*: pdwt_amd/boundary.py).  Every method is written
+// wt_ext.cpp -- host side of the four boundary-mode classes of include/wt_ext.h, `BoundaryWavelets` (2-D), `BoundaryWavelets1D` (the
+// last axis of a batch of rows), `BoundaryWavelets3D` (volumes) and `BoundaryWaveletsImages` (every image of a batch), above the
+// "... with boundary modes" entry points of include/pdwt_hip.h, and their flat C handle APIs (pdwt_bw_*, pdwt_bw1_*, pdwt_bw3_*,
+// pdwt_bwb_*: pdwt_amd/boundary.py).  Every method is written
 // once, on their base `BoundaryTransform`; what differs between the classes is one `bw_ops` table each, and of code only the scratch
 // and the walk over the levels.  Plain host C++ like wt.cpp, built into libpdwt.so (float) and libpdwtd.so (-DDOUBLEPRECISION).  The
 // geometry and the band table live here; thresholds, norms and statistics go through the band-list entries (bandstats_host.hpp): no
@@ -27,10 +28,11 @@ struct bw_priv {
     int dev;           // the device current at construction; every method runs there
     int L, mode;       // winfos.nlevels after clamping, winfos.mode
     int n[3][kL + 1];  // per axis: [0] the input, [l] the bands of level l (an axis that is not transformed keeps its size)
-    int fused;         // 1-D: the transforms of this instance are one launch each
+    int fused;         // 1-D, batch: the transforms of this instance are one launch each
     DTYPE* d_bands;    // the one allocation behind d_coeffs
     DTYPE* d_tmp[2];   // the scratch of the level walk (see the three walks below); NULL where the walk needs none
     long long approx_off;  // 3-D: where the approximation of the levels 1 .. L-1 lies in d_tmp[0]
+    void* d_tab;       // batch: the device table of the B * nb per-image band pointers of the images_* methods, built on first use
 };
 inline bw_priv* P(void* p) { return (bw_priv*)p; }
 }  // namespace
@@ -49,6 +51,7 @@ struct bw_ops {
     int (*alloc_scratch)(bw_priv*, int rc);  // after the image and the bands, whose result is rc: the scratch of the walk; the new rc
     int (*forward)(BoundaryTransform&, bw_priv*);  // all levels; PDWT_OK or the code of the entry that failed
     int (*inverse)(BoundaryTransform&, bw_priv*);
+    int max_batch;  // the batch of images: the largest dims[0] (part of the size check); 0: dims[0] is no batch
 };
 
 namespace {
@@ -181,10 +184,34 @@ int walk3(BoundaryTransform& W, bw_priv* p, bool fwd)
 int forward3(BoundaryTransform& W, bw_priv* p) { return walk3(W, p, true); }
 int inverse3(BoundaryTransform& W, bw_priv* p) { return walk3(W, p, false); }
 
-const bw_ops kOps2 = {"BoundaryWavelets", 2, BW_MAX_LEVELS, 3, false, "image", "a %dx%d image", "is too small", NULL, alloc2, forward2, inverse2};
-const bw_ops kOps1 = {"BoundaryWavelets1D", 1, BW_MAX_LEVELS, 1, false, "batch", "rows of %d samples", "are too short", NULL, alloc1, forward1, inverse1};
+// Batch of images.  As 1-D: the whole-transform entries choose between the one-launch kernels (one workgroup per image) and the
+// per-level loop over the stacks; the scratch is that of the loop (two level-1 stacks), sized by the library, none when fused.
+int allocb(bw_priv* p, int rc)
+{
+    const long long ntmp = pdwt_ext2db_tmp_elems(p->n[0][0], p->n[1][0], p->n[2][0], p->f.hlen, p->L, (int)sizeof(DTYPE));
+    p->fused = pdwt_ext2db_fused(p->n[1][0], p->n[2][0], p->f.hlen, p->L, (int)sizeof(DTYPE)) == 1;
+    if (ntmp < 0) return PDWT_ENOMEM;
+    if (rc != PDWT_OK || ntmp == 0) return rc;
+    p->d_tmp[0] = (DTYPE*)pdwt_malloc((size_t)ntmp * sizeof(DTYPE));
+    return p->d_tmp[0] ? PDWT_OK : PDWT_ENOMEM;
+}
+int forwardb(BoundaryTransform& W, bw_priv* p)
+{
+    const int rc = SFX(pdwt_ext2db_forward)(W.d_image, W.d_coeffs, p->n[0][0], p->n[1][0], p->n[2][0], p->L, p->mode, &p->f, p->d_tmp[0]);
+    return rc < 0 ? rc : PDWT_OK;
+}
+int inverseb(BoundaryTransform& W, bw_priv* p)
+{
+    const int rc = SFX(pdwt_ext2db_inverse)(W.d_image, W.d_coeffs, p->n[0][0], p->n[1][0], p->n[2][0], p->L, &p->f, p->d_tmp[0]);
+    return rc < 0 ? rc : PDWT_OK;
+}
+
+const bw_ops kOps2 = {"BoundaryWavelets", 2, BW_MAX_LEVELS, 3, false, "image", "a %dx%d image", "is too small", NULL, alloc2, forward2, inverse2, 0};
+const bw_ops kOps1 = {"BoundaryWavelets1D", 1, BW_MAX_LEVELS, 1, false, "batch", "rows of %d samples", "are too short", NULL, alloc1, forward1, inverse1, 0};
 const bw_ops kOps3 = {"BoundaryWavelets3D", 3, BW3_MAX_LEVELS, 7, true, "volume", "a %dx%dx%d volume", "is too small",
-                      "unsupported volume size (Nz <= 65535 and Nr * Nc < 2^31 are required)", alloc3, forward3, inverse3};
+                      "unsupported volume size (Nz <= 65535 and Nr * Nc < 2^31 are required)", alloc3, forward3, inverse3, 0};
+const bw_ops kOpsB = {"BoundaryWaveletsImages", 2, BW_MAX_LEVELS, 3, false, "image batch", "%dx%d images", "are too small", NULL, allocb, forwardb, inverseb,
+                      BWB_MAX_IMAGES};
 }  // namespace
 #define ON_MY_DEVICE_B() DevScope dev_scope_(priv_ ? ((const bw_priv*)priv_)->dev : -1)
 
@@ -198,7 +225,7 @@ void BoundaryTransform::create(const bw_ops& o, DTYPE* src, const int* dims, con
     wname[127] = 0;
     state = W_CREATION_ERROR;  // until the last line
     // (3-D states its limits in a message of its own, below)
-    const bool too_large = !o.unsupported && (unsigned long long)dims[1] * (unsigned long long)dims[2] >= (1ull << 31);
+    const bool too_large = (!o.unsupported && (unsigned long long)dims[1] * (unsigned long long)dims[2] >= (1ull << 31)) || (o.max_batch && dims[0] > o.max_batch);
     if (dims[0] < 1 || dims[1] < 1 || dims[2] < 1 || !wname_ || too_large) {
         printf("ERROR: %s(): invalid %s size or wavelet name\n", o.name, o.noun);
         return;
@@ -283,6 +310,7 @@ BoundaryTransform::~BoundaryTransform()
         if (p->d_bands) pdwt_free(p->d_bands);
         if (p->d_tmp[0]) pdwt_free(p->d_tmp[0]);
         if (p->d_tmp[1]) pdwt_free(p->d_tmp[1]);
+        if (p->d_tab) pdwt_free(p->d_tab);
         delete p;
     }
 }
@@ -306,6 +334,13 @@ BoundaryWavelets3D::BoundaryWavelets3D(DTYPE* vol, int Nz, int Nr, int Nc, const
     const int dims[3] = {Nz, Nr, Nc};
     winfos.Nz = Nz, winfos.Nr = Nr, winfos.Nc = Nc, winfos.nlevels = levels, winfos.hlen = 0, winfos.mode = mode;
     create(kOps3, vol, dims, wname_, mode, memisonhost, &winfos.nlevels, &winfos.hlen);
+}
+
+BoundaryWaveletsImages::BoundaryWaveletsImages(DTYPE* imgs, int B, int Nr, int Nc, const char* wname_, int levels, int mode, int memisonhost)
+{
+    const int dims[3] = {B, Nr, Nc};
+    winfos.B = B, winfos.Nr = Nr, winfos.Nc = Nc, winfos.nlevels = levels, winfos.hlen = 0, winfos.mode = mode;
+    create(kOpsB, imgs, dims, wname_, mode, memisonhost, &winfos.nlevels, &winfos.hlen);
 }
 
 // ---- the static geometry of each class: its own size check, then the shared rule -------------------------------------------------------
@@ -406,6 +441,7 @@ void BoundaryTransform::set_image(DTYPE* img, int mem_is_on_device)
 
 int BoundaryTransform::num_bands() const { return state == W_CREATION_ERROR ? 0 : ops_->per_level * P(priv_)->L + 1; }
 int BoundaryWavelets1D::fused() const { return state == W_CREATION_ERROR || !priv_ ? 0 : P(priv_)->fused; }
+int BoundaryWaveletsImages::fused() const { return state == W_CREATION_ERROR || !priv_ ? 0 : P(priv_)->fused; }
 
 long long BoundaryTransform::band_shape(int num, int* shape) const
 {
@@ -434,6 +470,16 @@ long long BoundaryWavelets3D::coeff_shape(int num, int* nz, int* nr, int* nc) co
     int s[3];
     const long long n = band_shape(num, s);
     if (n > 0 && nz) *nz = s[0];
+    if (n > 0 && nr) *nr = s[1];
+    if (n > 0 && nc) *nc = s[2];
+    return n;
+}
+
+long long BoundaryWaveletsImages::coeff_shape(int num, int* b, int* nr, int* nc) const
+{
+    int s[3];
+    const long long n = band_shape(num, s);
+    if (n > 0 && b) *b = s[0];
     if (n > 0 && nr) *nr = s[1];
     if (n > 0 && nc) *nc = s[2];
     return n;
@@ -591,7 +637,117 @@ double BoundaryTransform::denoise(int method, double sigma, int kind, DTYPE* bet
     return sigma;
 }
 
-// ---- flat C handle APIs (pdwt_amd/boundary.py): the same functions under three prefixes; new, info, geometry, coeff_shape (and fused)
+// ---- the batch of images, per image (the semantics of WaveletsImages, wt.cpp): the batch entries of bandstats_host.hpp over the slices
+// of the stacks --------------------------------------------------------------------------------------------------------------------
+namespace {
+// the band geometry of ONE image (ptr[] = the slices of image 0) and the device table of all B * nb slices; nb = 0: refused
+pdwt_bl::BandList image_geometry(const BoundaryTransform& W, const bw_ops* o, bw_priv* p, bool need_forward, DTYPE* const** tab)
+{
+    pdwt_bl::BandList g = band_list(W, o, p, need_forward);
+    *tab = NULL;
+    if (!g.nb) return g;
+    const int B = p->n[0][0];
+    for (int k = 0; k < g.nb; k++) g.n[k] /= (size_t)B;
+    if (!p->d_tab) {  // (set_coeff copies INTO the stacks and no method moves them: built once)
+        DTYPE** host = new (std::nothrow) DTYPE*[(size_t)B * g.nb];
+        void* d = host ? pdwt_malloc((size_t)B * g.nb * sizeof(DTYPE*)) : NULL;
+        if (d) {
+            for (int b = 0; b < B; b++)
+                for (int k = 0; k < g.nb; k++) host[(size_t)b * g.nb + k] = W.d_coeffs[k] + (size_t)b * g.n[k];
+            if (pdwt_memcpy_h2d(d, host, (size_t)B * g.nb * sizeof(DTYPE*)) != PDWT_OK) {
+                pdwt_free(d);
+                d = NULL;
+            }
+        }
+        delete[] host;
+        p->d_tab = d;
+    }
+    *tab = (DTYPE* const*)p->d_tab;
+    return g;
+}
+}  // namespace
+
+int BoundaryWaveletsImages::images_all_band_stats(w_band_stats* out, int with_median)
+{
+    ON_MY_DEVICE_B();
+    DTYPE* const* tab;
+    const pdwt_bl::BandList g = image_geometry(*this, ops_, P(priv_), true, &tab);
+    if (!g.nb || !out) return PDWT_EINVAL;
+    if (!tab) return PDWT_ENOMEM;
+    const int rc = pdwt_bl::batch_stats(g, tab, winfos.B, out, with_median);
+    if (rc != PDWT_OK) report(ops_->name, "::images_all_band_stats()", rc);
+    return rc;
+}
+
+int BoundaryWaveletsImages::images_estimate_sigma(double* sigma_out)
+{
+    ON_MY_DEVICE_B();
+    DTYPE* const* tab;
+    const pdwt_bl::BandList g = image_geometry(*this, ops_, P(priv_), true, &tab);
+    if (!g.nb || !sigma_out) return PDWT_EINVAL;
+    if (!tab) return PDWT_ENOMEM;
+    pdwt_band_stats* s = new pdwt_band_stats[(size_t)winfos.B * g.nb];
+    const int rc = pdwt_bl::batch_estimate_sigma(g, tab, winfos.B, s, sigma_out);
+    delete[] s;
+    if (rc != PDWT_OK) report(ops_->name, "::images_estimate_sigma()", rc);
+    return rc;
+}
+
+int BoundaryWaveletsImages::images_threshold_bands(const DTYPE* betas, int kind)
+{
+    ON_MY_DEVICE_B();
+    DTYPE* const* tab;
+    const pdwt_bl::BandList g = image_geometry(*this, ops_, P(priv_), true, &tab);
+    if (!g.nb || !betas || (kind != 0 && kind != 1)) return PDWT_EINVAL;
+    if (!tab) return PDWT_ENOMEM;
+    const int rc = pdwt_bl::batch_threshold(g, tab, winfos.B, betas, kind);
+    if (rc != PDWT_OK) {
+        report(ops_->name, "::images_threshold_bands()", rc);
+        state = W_THRESHOLD_ERROR;
+    }
+    return rc;
+}
+
+int BoundaryWaveletsImages::images_denoise(int method, const double* sigma_in, int kind, double* sigma_out, DTYPE* betas_out)
+{
+    ON_MY_DEVICE_B();
+    DTYPE* const* tab;
+    const pdwt_bl::BandList g = image_geometry(*this, ops_, P(priv_), true, &tab);
+    if (!g.nb || !sigma_out || (method != 0 && method != 1) || (kind != 0 && kind != 1)) return PDWT_EINVAL;
+    if (!tab) return PDWT_ENOMEM;
+    const size_t cnt = (size_t)winfos.B * g.nb;
+    pdwt_band_stats* s = new pdwt_band_stats[cnt];
+    DTYPE* betas = betas_out ? betas_out : new DTYPE[cnt];
+    const int rc = pdwt_bl::batch_denoise(g, tab, winfos.B, method, kind, sigma_in, s, sigma_out, betas);
+    if (!betas_out) delete[] betas;
+    delete[] s;
+    if (rc != PDWT_OK) {
+        report(ops_->name, "::images_denoise()", rc);
+        state = W_THRESHOLD_ERROR;
+    }
+    return rc;
+}
+
+int BoundaryWaveletsImages::images_norm1(double* out)
+{
+    ON_MY_DEVICE_B();
+    DTYPE* const* tab;
+    const pdwt_bl::BandList g = image_geometry(*this, ops_, P(priv_), false, &tab);
+    if (!g.nb || !out) return PDWT_EINVAL;
+    if (!tab) return PDWT_ENOMEM;
+    w_band_stats* s = new w_band_stats[(size_t)winfos.B * g.nb];
+    const int rc = pdwt_bl::batch_stats(g, tab, winfos.B, s, 0);
+    for (int b = 0; b < winfos.B && rc == PDWT_OK; b++) {
+        double acc = 0.0;
+        for (int k = 0; k < g.nb; k++) acc += s[(size_t)b * g.nb + k].sum_abs;
+        out[b] = acc;
+    }
+    delete[] s;
+    if (rc != PDWT_OK) report(ops_->name, "::images_norm1()", rc);
+    return rc;
+}
+
+// ---- flat C handle APIs (pdwt_amd/boundary.py): the same functions under four prefixes; new, info, geometry, coeff_shape (and fused)
 // take the arguments of their class and are written out below ---------------------------------------------------------------------
 #define BW_HANDLE_API(pfx, Cls)                                                                                                                   \
     void pfx##delete(void* h) { delete static_cast<Cls*>(h); }                                                                                    \
@@ -622,6 +778,7 @@ extern "C" {
 BW_HANDLE_API(pdwt_bw_, BoundaryWavelets)
 BW_HANDLE_API(pdwt_bw1_, BoundaryWavelets1D)
 BW_HANDLE_API(pdwt_bw3_, BoundaryWavelets3D)
+BW_HANDLE_API(pdwt_bwb_, BoundaryWaveletsImages)
 
 void* pdwt_bw_new(DTYPE* img, int Nr, int Nc, const char* wname, int levels, int mode, int memisonhost)
 {
@@ -650,4 +807,21 @@ int pdwt_bw3_geometry(int Nz, int Nr, int Nc, int hlen, int levels, int* nz, int
     return BoundaryWavelets3D::geometry(Nz, Nr, Nc, hlen, levels, nz, nr, nc);
 }
 long long pdwt_bw3_coeff_shape(void* h, int num, int* nz, int* nr, int* nc) { return static_cast<BoundaryWavelets3D*>(h)->coeff_shape(num, nz, nr, nc); }
+
+void* pdwt_bwb_new(DTYPE* imgs, int B, int Nr, int Nc, const char* wname, int levels, int mode, int memisonhost)
+{
+    return new (std::nothrow) BoundaryWaveletsImages(imgs, B, Nr, Nc, wname, levels, mode, memisonhost);
+}
+void pdwt_bwb_info(void* h, w_info_bwb* out) { *out = static_cast<BoundaryWaveletsImages*>(h)->winfos; }
+int pdwt_bwb_geometry(int Nr, int Nc, int hlen, int levels, int* nr, int* nc) { return BoundaryWavelets::geometry(Nr, Nc, hlen, levels, nr, nc); }
+long long pdwt_bwb_coeff_shape(void* h, int num, int* b, int* nr, int* nc) { return static_cast<BoundaryWaveletsImages*>(h)->coeff_shape(num, b, nr, nc); }
+int pdwt_bwb_fused(void* h) { return static_cast<BoundaryWaveletsImages*>(h)->fused(); }
+int pdwt_bwb_images_all_band_stats(void* h, w_band_stats* out, int with_median) { return static_cast<BoundaryWaveletsImages*>(h)->images_all_band_stats(out, with_median); }
+int pdwt_bwb_images_estimate_sigma(void* h, double* sigma_out) { return static_cast<BoundaryWaveletsImages*>(h)->images_estimate_sigma(sigma_out); }
+int pdwt_bwb_images_threshold_bands(void* h, const DTYPE* betas, int kind) { return static_cast<BoundaryWaveletsImages*>(h)->images_threshold_bands(betas, kind); }
+int pdwt_bwb_images_denoise(void* h, int method, const double* sigma_in, int kind, double* sigma_out, DTYPE* betas_out)
+{
+    return static_cast<BoundaryWaveletsImages*>(h)->images_denoise(method, sigma_in, kind, sigma_out, betas_out);
+}
+int pdwt_bwb_images_norm1(void* h, double* out) { return static_cast<BoundaryWaveletsImages*>(h)->images_norm1(out); }
 }
