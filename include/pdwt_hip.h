@@ -686,6 +686,51 @@ int pdwt_wp1_moments_f64(const double* d_level, long long nseg, int n, double* o
 int pdwt_wp1_thresh_f32(int op, float* d_level, int nr, int nnodes, int n, const unsigned char* d_flags, float beta);
 int pdwt_wp1_thresh_f64(int op, double* d_level, int nr, int nnodes, int n, const unsigned char* d_flags, double beta);
 
+/* ---------------------------------------------------------------------------------------------
+ * Batched 2-D wavelet packets (pdwt_amd/csrc/wpt2db.hip; the class: WaveletPacketsImages, include/wpt_batch.h): the full quad-tree of
+ * the "2-D wavelet packets" above on every image of a B x Nr x Nc stack, the same arithmetic and the same bits per image.
+ * Storage: ONE allocation per depth l = 1 .. L laid out (B, 4^l, nr_l, nc_l) contiguous, image-major: image b's node i of depth l is
+ * forest node b 4^l + i, its children are the forest nodes 4 (b 4^l + i) + 0..3 of depth l + 1.  Depth 0 is the stack of images.
+ * 1 <= B <= 65535, Nr Nc < 2^31 and B 4^L <= 2^22; anything else, a NULL pointer, a bad bank length or levels that geometry does not
+ * give back unchanged is PDWT_EINVAL and nothing is launched.
+ *
+ * No device needed.  geometry: WaveletPackets::geometry -- the depth an image of this size gets (levels < 1 asks for 1; clamped to
+ * ilog2(min(Nr, Nc) / (hlen - 1)) and to 7; 0 = too small, a bad size or a bad bank length) and, in nr / nc when given, the node
+ * shapes of depth 0 .. that depth.  fused: 1 when the whole tree of an image runs in the LDS of one workgroup, one launch per
+ * direction (two image-sized buffers, the index tables and the state table fit 160 KiB: float32 up to about 128 x 128, float64 about
+ * 96 x 96), else 0.  lds_bytes: the dynamic LDS of the forward (dir 0) / inverse (dir 1) fused launch of that plan, whether it fits or
+ * not.  state_table: the node states of the inverse from a basis given as n (depth, idx) pairs, one byte per node, node i of depth l
+ * at (4^l - 1) / 3 + i, (4^(levels + 1) - 1) / 3 bytes: 1 = a node of the basis (loaded), 2 = above the basis (synthesised from its
+ * four children), 0 = below it (skipped); PDWT_EINVAL unless every root-to-leaf path meets exactly one of the nodes.
+ * tmp_elems: the INTS of the device list buffer the per-depth form of the inverse reads, 0 when the fused form runs (the plan says
+ * fused and allow_fused is set).  chunk_lists: fills that buffer on the HOST from a state table (lists == NULL: only counts) and
+ * returns its ints: per depth the chunk-relative indices of the parents to synthesise.  A chunk of the per-depth form is 16384
+ * forest parents, a whole number of images, so one list per depth serves every chunk.
+ *
+ * The whole-transform entries take d_nodes, a HOST table of levels device pointers (d_nodes[l - 1] = the allocation of depth l).
+ * forward fills every depth and leaves d_src intact.  inverse reconstructs d_dst (B x Nr x Nc) under `state`, a HOST state_table
+ * whose root is 2 (validated on every call); d_state is its DEVICE copy, read by the fused form; d_lists the DEVICE copy of
+ * chunk_lists, read by the per-depth form when a depth holds both parents to synthesise and others (else it may be NULL).  They
+ * return PDWT_WPTB_FUSED when one launch ran every tree -- the inverse then writes d_dst ONLY -- or PDWT_WPTB_LEVELS when the level
+ * entries of wpt2d.hip were looped over the forest (allow_fused == 0, or an image beyond the budget) in chunks of at most 16384
+ * parents -- the inverse then writes every synthesised parent to its own allocation first; the nodes of the basis are never
+ * modified.  Same bits on both paths.  Buffers need only be aligned to their element type.  Asynchronous on the library stream.
+ * ------------------------------------------------------------------------------------------- */
+#define PDWT_WPTB_LEVELS 0 /* the level entries ran, depth by depth */
+#define PDWT_WPTB_FUSED 1  /* one launch ran the whole tree of every image */
+int pdwt_wptb_geometry(int Nr, int Nc, int hlen, int levels, int* nr, int* nc);
+int pdwt_wptb_fused(int Nr, int Nc, int hlen, int levels, int elem_size);
+long long pdwt_wptb_lds_bytes(int Nr, int Nc, int hlen, int levels, int elem_size, int dir);
+long long pdwt_wptb_tmp_elems(int B, int Nr, int Nc, int hlen, int levels, int elem_size, int allow_fused);
+int pdwt_wptb_state_table(int levels, const int* depth, const int* idx, int n, unsigned char* out);
+long long pdwt_wptb_chunk_lists(int B, int levels, const unsigned char* state, int* lists);
+int pdwt_wptb_forward_f32(const float* d_src, float* const* d_nodes, int B, int Nr, int Nc, int levels, const pdwt_filters_f32* f, int allow_fused);
+int pdwt_wptb_forward_f64(const double* d_src, double* const* d_nodes, int B, int Nr, int Nc, int levels, const pdwt_filters_f64* f, int allow_fused);
+int pdwt_wptb_inverse_f32(float* d_dst, float* const* d_nodes, int B, int Nr, int Nc, int levels, const unsigned char* state, const unsigned char* d_state,
+                          const int* d_lists, const pdwt_filters_f32* f, int allow_fused);
+int pdwt_wptb_inverse_f64(double* d_dst, double* const* d_nodes, int B, int Nr, int Nc, int levels, const unsigned char* state, const unsigned char* d_state,
+                          const int* d_lists, const pdwt_filters_f64* f, int allow_fused);
+
 #ifdef __cplusplus
 }
 #endif

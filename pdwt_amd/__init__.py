@@ -10,7 +10,7 @@ from ._native import Info, Info3D, hip, host, require_gpu  # noqa: F401
 from .wavelets import DeviceArray, ImageBatch, Wavelets, W_CREATION_ERROR, W_FORWARD, W_INIT, W_INVERSE  # noqa: F401
 from .wavelets3d import Wavelets3D  # noqa: F401
 from .swt3d import StationaryWavelets3D  # noqa: F401
-from .wpt import WaveletPackets1D, WaveletPackets2D  # noqa: F401
+from .wpt import WaveletPacketBatch, WaveletPackets1D, WaveletPackets2D  # noqa: F401
 from .boundary import BoundaryImageBatch, BoundaryWavelets1D, BoundaryWavelets2D, BoundaryWavelets3D  # noqa: F401
 
-__all__ = ["Wavelets", "Wavelets3D", "StationaryWavelets3D", "WaveletPackets2D", "WaveletPackets1D", "BoundaryWavelets2D", "BoundaryWavelets1D", "BoundaryWavelets3D", "BoundaryImageBatch", "ImageBatch", "DeviceArray", "Info", "hip", "host", "require_gpu"]
+__all__ = ["Wavelets", "Wavelets3D", "StationaryWavelets3D", "WaveletPackets2D", "WaveletPackets1D", "WaveletPacketBatch", "BoundaryWavelets2D", "BoundaryWavelets1D", "BoundaryWavelets3D", "BoundaryImageBatch", "ImageBatch", "DeviceArray", "Info", "hip", "host", "require_gpu"]

@@ -28,6 +28,11 @@ class InfoWPT1(C.Structure):
     _fields_ = [("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int)]
 
 
+class InfoWPTB(C.Structure):
+    """== w_info_wptb (include/wpt_batch.h)."""
+    _fields_ = [("B", C.c_int), ("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int)]
+
+
 class InfoBW(C.Structure):
     """== w_info_bw (include/wt_ext.h)."""
     _fields_ = [("Nr", C.c_int), ("Nc", C.c_int), ("nlevels", C.c_int), ("hlen", C.c_int), ("mode", C.c_int)]
@@ -86,7 +91,8 @@ PLAIN_SYMBOLS = ["pdwt_device_count", "pdwt_set_device", "pdwt_get_device", "pdw
                  "pdwt_num_bands_ext1d", "pdwt_ext1d_band_len", "pdwt_ext1d_fused", "pdwt_ext1d_tmp_elems",
                  "pdwt_ext2db_fused", "pdwt_ext2db_tmp_elems",
                  "pdwt_num_bands_ext3d", "pdwt_ext3d_band_shape", "pdwt_ext3d_tmp_elems", "pdwt_ext3d_tmp_approx_offset",
-                 "pdwt_wp1_geometry", "pdwt_wp1_fused", "pdwt_wp1_tmp_elems", "pdwt_wp1_frequency_order", "pdwt_wp1_state_table", "pdwt_memcpy2d"]
+                 "pdwt_wp1_geometry", "pdwt_wp1_fused", "pdwt_wp1_tmp_elems", "pdwt_wp1_frequency_order", "pdwt_wp1_state_table", "pdwt_memcpy2d",
+                 "pdwt_wptb_geometry", "pdwt_wptb_fused", "pdwt_wptb_lds_bytes", "pdwt_wptb_tmp_elems", "pdwt_wptb_state_table", "pdwt_wptb_chunk_lists"]
 TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coeffs_buffer", "copy_coeffs_buffer",
                   "soft_thresh", "soft_thresh_sum", "norm1", "norm1_as_double", "norm1_enqueue", "hard_thresh", "proj_linf", "shrink", "group_soft_thresh",
                   "norm2sq", "norm2sq_as_double", "add_coeffs", "circshift", "forward_nonseparable", "inverse_nonseparable",
@@ -98,7 +104,8 @@ TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coe
                   "ext1d_forward_level", "ext1d_inverse_level", "ext1d_forward", "ext1d_inverse",
                   "ext3d_forward_level", "ext3d_inverse_level",
                   "ext2db_forward_level", "ext2db_inverse_level", "ext2db_forward", "ext2db_inverse",
-                  "wp1_forward_level", "wp1_inverse_level", "wp1_forward", "wp1_inverse", "wp1_moments", "wp1_thresh"] + DRIVERS + HAAR_DRIVERS)
+                  "wp1_forward_level", "wp1_inverse_level", "wp1_forward", "wp1_inverse", "wp1_moments", "wp1_thresh",
+                  "wptb_forward", "wptb_inverse"] + DRIVERS + HAAR_DRIVERS)
 
 _hip = None
 _host = {}
@@ -257,7 +264,18 @@ def hip():
         getattr(L, "pdwt_wp1_inverse_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, vp, C.POINTER(FT)]
         getattr(L, "pdwt_wp1_moments_" + sfx).argtypes = [vp, C.c_longlong, ci, C.POINTER(C.c_double)]
         getattr(L, "pdwt_wp1_thresh_" + sfx).argtypes = [ci, vp, ci, ci, ci, vp, ct]
+        getattr(L, "pdwt_wptb_forward_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, C.POINTER(FT), ci]
+        getattr(L, "pdwt_wptb_inverse_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, C.POINTER(C.c_ubyte), vp, vp, C.POINTER(FT), ci]
     L.pdwt_wp1_geometry.argtypes = [ci, ci, ci, C.POINTER(ci)]
+    L.pdwt_wptb_geometry.argtypes = [ci, ci, ci, ci, C.POINTER(ci), C.POINTER(ci)]
+    L.pdwt_wptb_fused.argtypes = [ci, ci, ci, ci, ci]
+    L.pdwt_wptb_lds_bytes.restype = C.c_longlong
+    L.pdwt_wptb_lds_bytes.argtypes = [ci, ci, ci, ci, ci, ci]
+    L.pdwt_wptb_tmp_elems.restype = C.c_longlong
+    L.pdwt_wptb_tmp_elems.argtypes = [ci, ci, ci, ci, ci, ci, ci]
+    L.pdwt_wptb_state_table.argtypes = [ci, C.POINTER(ci), C.POINTER(ci), ci, C.POINTER(C.c_ubyte)]
+    L.pdwt_wptb_chunk_lists.restype = C.c_longlong
+    L.pdwt_wptb_chunk_lists.argtypes = [ci, ci, C.POINTER(C.c_ubyte), C.POINTER(ci)]
     L.pdwt_wp1_fused.argtypes = [ci, ci, ci, ci]
     L.pdwt_wp1_tmp_elems.restype = C.c_longlong
     L.pdwt_wp1_tmp_elems.argtypes = [ci, ci, ci, ci, ci]
@@ -441,6 +459,39 @@ def host(dtype):
         L.pdwt_wp1h_node_stats.argtypes = [vp, ci, C.POINTER(BandStats)]
         L.pdwt_wp1h_estimate_sigma.restype = C.c_double
         L.pdwt_wp1h_estimate_sigma.argtypes = [vp]
+        # WaveletPacketsImages (include/wpt_batch.h, wptb.cpp)
+        L.pdwt_wpbh_new.restype = vp
+        L.pdwt_wpbh_new.argtypes = [vp, ci, ci, ci, C.c_char_p, ci, ci, ci]
+        for n in ("delete", "forward", "inverse", "state", "basis_size", "fused"):
+            getattr(L, "pdwt_wpbh_" + n).argtypes = [vp]
+        L.pdwt_wpbh_get_image.restype = C.c_longlong
+        L.pdwt_wpbh_get_image.argtypes = [vp, vp]
+        L.pdwt_wpbh_set_image.argtypes = [vp, vp, ci]
+        L.pdwt_wpbh_info.argtypes = [vp, C.POINTER(InfoWPTB)]
+        L.pdwt_wpbh_node_shape.restype = C.c_longlong
+        L.pdwt_wpbh_node_shape.argtypes = [vp, ci, pi, pi]
+        L.pdwt_wpbh_path_index.argtypes = [C.c_char_p, pi]
+        L.pdwt_wpbh_geometry.argtypes = [ci, ci, ci, ci, pi, pi]
+        for n in ("get_node", "get_level", "set_node"):
+            getattr(L, "pdwt_wpbh_" + n).restype = C.c_longlong
+        L.pdwt_wpbh_get_node.argtypes = [vp, vp, ci, ci]
+        L.pdwt_wpbh_get_level.argtypes = [vp, vp, ci]
+        L.pdwt_wpbh_set_node.argtypes = [vp, vp, ci, ci, ci]
+        L.pdwt_wpbh_node_int_ptr.restype = C.c_ssize_t
+        L.pdwt_wpbh_node_int_ptr.argtypes = [vp, ci, ci, C.POINTER(C.c_longlong)]
+        L.pdwt_wpbh_node_costs.argtypes = [vp, ci, ci, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        L.pdwt_wpbh_best_basis.argtypes = [vp, ci]
+        L.pdwt_wpbh_set_basis.argtypes = [vp, pi, pi, ci]
+        L.pdwt_wpbh_get_basis.argtypes = [vp, pi, pi]
+        for n in ("soft_threshold", "hard_threshold"):
+            getattr(L, "pdwt_wpbh_" + n).argtypes = [vp, ct, ci]
+        L.pdwt_wpbh_norm1.restype = C.c_double
+        L.pdwt_wpbh_norm1.argtypes = [vp]
+        L.pdwt_wpbh_images_norm1.argtypes = [vp, C.POINTER(C.c_double)]
+        L.pdwt_wpbh_node_stats.argtypes = [vp, ci, C.POINTER(BandStats)]
+        L.pdwt_wpbh_estimate_sigma.restype = C.c_double
+        L.pdwt_wpbh_estimate_sigma.argtypes = [vp]
+        L.pdwt_wpbh_images_estimate_sigma.argtypes = [vp, C.POINTER(C.c_double)]
         # BoundaryWavelets (include/wt_ext.h, wt_ext.cpp)
         L.pdwt_bw_new.restype = vp
         L.pdwt_bw_new.argtypes = [vp, ci, ci, C.c_char_p, ci, ci, ci]

@@ -1,8 +1,8 @@
 """Build the native libraries of pdwt_amd IN-TREE (pdwt_amd/lib/):
 
   libpdwt_hip.so   hand-written gfx950 kernels + the C-ABI of include/pdwt_hip.h   (hipcc)
-  libpdwt.so       host C++ `Wavelets` / `Wavelets3D` / `StationaryWavelets3D` / `WaveletPackets` / `WaveletPackets1D` / `BoundaryWavelets` / `BoundaryWavelets1D` / `BoundaryWavelets3D` / `BoundaryWaveletsImages`, DTYPE=float   (g++)
-  libpdwtd.so      host C++ `Wavelets` / `Wavelets3D` / `StationaryWavelets3D` / `WaveletPackets` / `WaveletPackets1D` / `BoundaryWavelets` / `BoundaryWavelets1D` / `BoundaryWavelets3D` / `BoundaryWaveletsImages`, DTYPE=double  (g++)
+  libpdwt.so       host C++ `Wavelets` / `Wavelets3D` / `StationaryWavelets3D` / `WaveletPackets` / `WaveletPackets1D` / `BoundaryWavelets` / `BoundaryWavelets1D` / `BoundaryWavelets3D` / `BoundaryWaveletsImages` / `WaveletPacketsImages`, DTYPE=float   (g++)
+  libpdwtd.so      host C++ `Wavelets` / `Wavelets3D` / `StationaryWavelets3D` / `WaveletPackets` / `WaveletPackets1D` / `BoundaryWavelets` / `BoundaryWavelets1D` / `BoundaryWavelets3D` / `BoundaryWaveletsImages` / `WaveletPacketsImages`, DTYPE=double  (g++)
 
 The two host libraries mirror the reference's product shape (Makefile:29-39).  hipcc cross-compiles
 for gfx950 without a GPU, so this runs in the build container; the .so files travel to the GPU box
@@ -20,10 +20,10 @@ LIB = os.path.join(PKG, "lib")
 INC = os.path.join(ROOT, "include")
 
 # (the slowest translation units first: the pool starts jobs in this order, and the build's wall time is the longest chain)
-HIP_SOURCES = ["dwt_lat.hip", "dwt_ext2db.hip", "swt_fused_l2_fwd.hip", "swt_fused_l2_inv.hip", "swt_fused_l2_inv1.hip", "swt_fused_l2_inv2.hip", "swt_fused_l2_inv4.hip", "dwt_lds.hip", "dwt_casc_inv3.hip", "dwt_casc.hip", "dwt_casc_invw.hip", "swt_fused_inv.hip", "swt_fused_invp.hip", "swt_fused_fwd.hip", "swt_fused_fwd_long.hip", "swt_fused_inv_long.hip", "swt_fused_f64_fwd.hip", "swt_fused_f64_inv.hip", "dwt1d_fused.hip", "dwt1d_fused_nt.hip", "dwt_stream.hip", "cols_ring_dwt_f32.hip", "cols_ring_dwt_f64.hip", "cols_ring_swt_f32.hip", "cols_ring_swt_f64.hip", "rows_tr.hip", "runtime.hip", "coeffs.hip", "dwt.hip", "swt.hip", "haar.hip", "utils.hip", "bandstats.hip", "bandbatch.hip", "nonsep.hip", "dwt3d.hip", "swt3d.hip", "wpt2d.hip", "dwt_ext.hip", "dwt_ext1d.hip", "wpt1d.hip", "dwt_ext3d.hip", "collective.hip", "selfcheck.hip", "filters.cpp"]
-HOST_SOURCES = ["wt.cpp", "wt_capi.cpp", "wt3d.cpp", "wpt.cpp", "wpt1d.cpp", "wt_ext.cpp"]
+HIP_SOURCES = ["dwt_lat.hip", "dwt_ext2db.hip", "wpt2db.hip", "swt_fused_l2_fwd.hip", "swt_fused_l2_inv.hip", "swt_fused_l2_inv1.hip", "swt_fused_l2_inv2.hip", "swt_fused_l2_inv4.hip", "dwt_lds.hip", "dwt_casc_inv3.hip", "dwt_casc.hip", "dwt_casc_invw.hip", "swt_fused_inv.hip", "swt_fused_invp.hip", "swt_fused_fwd.hip", "swt_fused_fwd_long.hip", "swt_fused_inv_long.hip", "swt_fused_f64_fwd.hip", "swt_fused_f64_inv.hip", "dwt1d_fused.hip", "dwt1d_fused_nt.hip", "dwt_stream.hip", "cols_ring_dwt_f32.hip", "cols_ring_dwt_f64.hip", "cols_ring_swt_f32.hip", "cols_ring_swt_f64.hip", "rows_tr.hip", "runtime.hip", "coeffs.hip", "dwt.hip", "swt.hip", "haar.hip", "utils.hip", "bandstats.hip", "bandbatch.hip", "nonsep.hip", "dwt3d.hip", "swt3d.hip", "wpt2d.hip", "dwt_ext.hip", "dwt_ext1d.hip", "wpt1d.hip", "dwt_ext3d.hip", "collective.hip", "selfcheck.hip", "filters.cpp"]
+HOST_SOURCES = ["wt.cpp", "wt_capi.cpp", "wt3d.cpp", "wpt.cpp", "wpt1d.cpp", "wt_ext.cpp", "wptb.cpp"]
 # (kept for reference; an object's real dependencies are the files its source includes, transitively: _deps())
-HIP_DEPS = ["common.hpp", "dwt_stream.hpp", "stream_dev.hpp", "dwt_casc.hpp", "casc_dev.hpp", "dwt_lds.hpp", "swt_fused.hpp", "swt_fused.inc", "swt_fused_l2.inc", "swt_fused_f64.inc", "dwt1d_fused.hpp", "cols_ring.hpp", "cols_ring.inc", "rows_tr.hpp", "tapreg.hpp", "filters_table.inc", "bandlist.hpp", "vol3d.hpp", "dwt_ext.hpp", "dwt_ext1d.hpp", "wpt1d.hpp", "dwt_ext3d_xy.hpp", "dwt_ext2db.hpp"]
+HIP_DEPS = ["common.hpp", "dwt_stream.hpp", "stream_dev.hpp", "dwt_casc.hpp", "casc_dev.hpp", "dwt_lds.hpp", "swt_fused.hpp", "swt_fused.inc", "swt_fused_l2.inc", "swt_fused_f64.inc", "dwt1d_fused.hpp", "cols_ring.hpp", "cols_ring.inc", "rows_tr.hpp", "tapreg.hpp", "filters_table.inc", "bandlist.hpp", "vol3d.hpp", "dwt_ext.hpp", "dwt_ext1d.hpp", "wpt1d.hpp", "dwt_ext3d_xy.hpp", "dwt_ext2db.hpp", "wpt2db.hpp"]
 ARCH = "gfx950"
 
 

@@ -1,6 +1,6 @@
 """Python views of the C++ wavelet packet classes: ``WaveletPackets`` (include/wpt.h), the 2-D transform -- the full quad-tree, in which
-every band is decomposed again -- and ``WaveletPackets1D`` (include/wpt1d.h), the full binary tree of every row of a batch; both with
-best-basis selection.
+every band is decomposed again --, ``WaveletPackets1D`` (include/wpt1d.h), the full binary tree of every row of a batch, and
+``WaveletPacketsImages`` (include/wpt_batch.h), the quad-tree of every image of a stack; all with best-basis selection.
 
 A node is named by a path string with one letter per depth, the first level the most significant, or by a ``(depth, idx)`` pair.  2-D:
 ``a h v d`` = digits 0 1 2 3, ``"ahd"`` is node 7 of depth 3, node ``i`` of depth ``l`` has the children ``4i .. 4i+3``.  1-D: ``a d`` =
@@ -355,4 +355,155 @@ class WaveletPackets1D(WaveletPackets2D):
             if self._fn("node_costs")(self._h, d, COSTS[cost], c.ctypes.data_as(C.POINTER(C.c_double)), pr.ctypes.data_as(C.POINTER(C.c_double))) != 0:
                 raise RuntimeError("node_costs refused (state=%d): the coefficients are not valid" % self.state)
             out.append(pr if per_row else c)
+        return out
+
+
+class StackDeviceArray(PitchedDeviceArray):
+    """Zero-copy view of a stack of B contiguous (nr, nc) blocks ``pitch`` ELEMENTS apart (a node of ``WaveletPacketBatch`` across the
+    images).  ``__cuda_array_interface__`` carries the strides."""
+
+    @property
+    def __cuda_array_interface__(self):
+        isz = self.dtype.itemsize
+        return {"shape": self.shape, "typestr": self.dtype.str, "data": (self.ptr, False), "version": 2,
+                "strides": (self.pitch * isz, self.shape[2] * isz, isz)}
+
+    def numpy(self):
+        out = np.empty(self.shape, dtype=self.dtype)
+        w = self.shape[1] * self.shape[2] * self.dtype.itemsize
+        if N.hip().pdwt_memcpy2d(out.ctypes.data_as(C.c_void_p), w, C.c_void_p(self.ptr), self.pitch * self.dtype.itemsize, w, self.shape[0], 1) != 0:
+            raise RuntimeError("device-to-host copy failed")
+        return out
+
+
+class WaveletPacketBatch(WaveletPackets2D):
+    """WaveletPacketBatch(imgs, wname, levels, dtype=None, allow_fused=True): the packet quad-tree of every image of a stack ``(B, Nr, Nc)``
+    -- a numpy array or a contiguous float32 / float64 device tensor (copied device to device) -- each image exactly as
+    ``WaveletPackets2D`` would transform it (the same bits).  Depth ``l`` is stored as ``(B, 4^l, nr_l, nc_l)``; ONE basis serves the
+    whole batch, chosen by ``best_basis`` from the costs summed over the images.  Same methods and state machine as
+    ``WaveletPackets2D``; ``node_shape(depth)`` is the shape of one node of one image.  ``fused``: the whole tree of an image runs in the
+    LDS of one workgroup, one launch per direction (``allow_fused=False``: depth by depth over the forest of all images).  Device
+    memory about (levels + 1) batches.  Only what the batch changes is written here."""
+
+    _hpfx, _arity, _info_t = "pdwt_wpbh_", 4, N.InfoWPTB
+    _err_shape = "WaveletPacketBatch needs a stack of images (B, Nr, Nc)"
+    _err_alloc = "WaveletPacketBatch allocation failed"
+
+    def __init__(self, imgs, wname, levels, dtype=None, allow_fused=True):
+        N.require_gpu()
+        dev = _device_source(imgs)
+        if dev is not None:
+            ptr, shape, dt = dev
+            if dtype is not None and np.dtype(dtype) != dt:
+                raise TypeError("dtype does not match the device tensor")
+            _sync_producer()
+            src, on_host, keep = C.c_void_p(ptr), 0, None
+        else:
+            imgs = np.asarray(imgs)
+            dt = np.dtype(dtype or (imgs.dtype if imgs.dtype in (np.float32, np.float64) else np.float32))
+            keep = np.ascontiguousarray(imgs, dtype=dt)
+            shape, src, on_host = keep.shape, keep.ctypes.data_as(C.c_void_p), 1
+        if len(shape) != 3:
+            raise ValueError(self._err_shape)
+        self.dtype, self.shape, self.wname = np.dtype(dt), tuple(int(v) for v in shape), wname
+        self._L = N.host(self.dtype)
+        self._ct = C.c_float if self.dtype == np.float32 else C.c_double
+        self._h = self._fn("new")(src, self.shape[0], self.shape[1], self.shape[2], wname.encode(), int(levels), on_host, 1 if allow_fused else 0)
+        del keep
+        if not self._h:
+            raise MemoryError(self._err_alloc)
+
+    @property
+    def fused(self):
+        return bool(self._fn("fused")(self._h))
+
+    def set_image(self, imgs):
+        """Replace the whole stack ``(B, Nr, Nc)``."""
+        self._upload(self._fn("set_image"), imgs, self.shape[0] * self.shape[1] * self.shape[2])
+
+    def get_level(self, depth):
+        """All nodes of ``depth`` as one array of shape (B, 4^depth, nr, nc)."""
+        self._need_coeffs("get_level")
+        out = np.empty((self.shape[0], 4 ** int(depth)) + self.node_shape(depth), dtype=self.dtype)
+        if self._fn("get_level")(self._h, out.ctypes.data_as(C.c_void_p), int(depth)) != out.size:
+            raise RuntimeError("get_level(%d) failed (state=%d)" % (depth, self.state))
+        return out
+
+    def get_node(self, node):
+        """One node across the images: shape (B, nr, nc)."""
+        self._need_coeffs("get_node")
+        d, i = self._node(node)
+        out = np.empty((self.shape[0],) + self.node_shape(d), dtype=self.dtype)
+        if self._fn("get_node")(self._h, out.ctypes.data_as(C.c_void_p), d, i) != out.size:
+            raise RuntimeError("get_node(%r) failed (state=%d)" % (node, self.state))
+        return out
+
+    def set_node(self, node, arr):
+        """Overwrite one node in every image (a ``(B, nr, nc)`` numpy array or device tensor); the state becomes W_THRESHOLD."""
+        if self.state not in (W_FORWARD, W_THRESHOLD):
+            raise RuntimeError("set_node refused (state=%d): run forward() first" % self.state)
+        d, i = self._node(node)
+        r, c = self.node_shape(d)
+        n = self.shape[0] * r * c
+        if self._upload(self._fn("set_node"), arr, n, d, i) != n:
+            raise RuntimeError("set_node(%r) failed (state=%d)" % (node, self.state))
+
+    def node_int_ptr(self, node):
+        """Device address of the node of image 0; see ``node_pitch``."""
+        d, i = self._node(node)
+        return self._fn("node_int_ptr")(self._h, d, i, None)
+
+    def node_pitch(self, node):
+        """Distance between the node of consecutive images, in elements: 4^depth * nr * nc."""
+        d, i = self._node(node)
+        p = C.c_longlong()
+        self._fn("node_int_ptr")(self._h, d, i, C.byref(p))
+        return p.value
+
+    def node_view(self, node):
+        """One node across the images as a zero-copy strided ``StackDeviceArray`` (B, nr, nc) (call ``sync()`` before a consumer on
+        another stream reads it)."""
+        d, _ = self._node(node)
+        return StackDeviceArray(self, self.node_int_ptr(node), (self.shape[0],) + self.node_shape(d), self.dtype, self.node_pitch(node))
+
+    def level_view(self, depth):
+        """A whole depth as a zero-copy contiguous DeviceArray (B, 4^depth, nr, nc); depth 0: the images (B, 1, Nr, Nc)."""
+        return DeviceArray(self, self._fn("node_int_ptr")(self._h, int(depth), 0, None), (self.shape[0], 4 ** int(depth)) + self.node_shape(depth), self.dtype)
+
+    def node_costs(self, cost="shannon", per_image=False):
+        """[float64 array of 4^depth costs for depth 0 .. levels], summed over the images in image order; ``per_image=True``: arrays of
+        shape (B, 4^depth) instead.  Sums in double, combined in a fixed order: two runs give the same bits."""
+        if cost not in COSTS:
+            raise ValueError("cost must be 'l1' or 'shannon'")
+        out = []
+        for d in range(self.levels + 1):
+            c = np.empty(4 ** d, dtype=np.float64)
+            pi = np.empty((self.shape[0], 4 ** d), dtype=np.float64)
+            if self._fn("node_costs")(self._h, d, COSTS[cost], pi.ctypes.data_as(C.POINTER(C.c_double)), c.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+                raise RuntimeError("node_costs refused (state=%d): the coefficients are not valid" % self.state)
+            out.append(pi if per_image else c)
+        return out
+
+    def node_stats(self, depth):
+        """{sum_abs, sum_sq, max_abs: float64 arrays (B, 4^depth)} of every node of ``depth`` of every image, one batched launch."""
+        n = self.shape[0] * 4 ** int(depth)
+        self.node_shape(depth)
+        out = (N.BandStats * n)()
+        if self._fn("node_stats")(self._h, int(depth), out) != 0:
+            raise RuntimeError("node_stats refused (state=%d): the coefficients are not valid" % self.state)
+        a = np.frombuffer(out, dtype=np.float64).reshape(self.shape[0], 4 ** int(depth), 5)
+        return {"sum_abs": a[..., 1].copy(), "sum_sq": a[..., 2].copy(), "max_abs": a[..., 3].copy()}
+
+    def images_norm1(self):
+        """Sum of |c| over the nodes of the basis, per image: float64 array (B,)."""
+        out = np.empty(self.shape[0], dtype=np.float64)
+        if self._fn("images_norm1")(self._h, out.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+            raise RuntimeError("images_norm1 refused (state=%d): the coefficients are not valid" % self.state)
+        return out
+
+    def images_estimate_sigma(self):
+        """Noise level of each image from its own node ``"d"``: float64 array (B,).  ``estimate_sigma()`` pools all images."""
+        out = np.empty(self.shape[0], dtype=np.float64)
+        if self._fn("images_estimate_sigma")(self._h, out.ctypes.data_as(C.POINTER(C.c_double))) != 0:
+            raise RuntimeError("images_estimate_sigma refused (state=%d): the coefficients are not valid" % self.state)
         return out
