@@ -592,6 +592,45 @@ int pdwt_ext2db_inverse_f32(float* d_dst, float* const* d_coeffs, int B, int Nr,
 int pdwt_ext2db_inverse_f64(double* d_dst, double* const* d_coeffs, int B, int Nr, int Nc, int levels, const pdwt_filters_f64* f, double* d_tmp);
 
 /* ---------------------------------------------------------------------------------------------
+ * Adjoints of the boundary-mode DWT (pdwt_amd/csrc/dwt_ext_adj.hip): the transposes W^T and S^T of the linear maps that
+ * pdwt_ext2db_forward_* / pdwt_ext1d_forward_* (W, depends on the mode) and pdwt_ext2db_inverse_* / pdwt_ext1d_inverse_* (S) compute --
+ * what a gradient needs.  With a signal extension W^T is not S.  One level along one line (the notation of the sections above),
+ * cotangents abar, dbar of N entries:
+ *   u[s]    = sum_i abar[i] L[2i + 1 - s] + dbar[i] H[2i + 1 - s]   over the i whose tap index lies in 0 .. F-1,  s = 2 - F .. 2N - 1
+ *   xbar[k] = sum of u[s] over the s that the mode maps to sample k (s = k included), in ascending s
+ * In 2-D the column adjoint runs before the row adjoint: xbar[y][x] is the sum over the pre-images sy of y (ascending) of the sum over
+ * the pre-images sx of x (ascending) of the separable synthesis U[sy][sx] onto the extended grid.  Several levels run from the coarsest to
+ * the finest; the xbar of a level is the A cotangent of the next finer one.  The sums are gathers in that fixed order (no atomics): a
+ * result does not depend on B or on tiling, and two runs give the same bits.
+ * The adjoint of the inverse, abar[i] = sum_k xbar[k] IL[k + F - 2 - 2i], is the FORWARD transform in mode 0 (zero) with the bank
+ * L' = IL reversed, H' = IH reversed: the inverse_adjoint entries build that bank and run the forward entries (fused forms included);
+ * their return code is that of the forward entry and their scratch is pdwt_ext2db_tmp_elems / pdwt_ext1d_tmp_elems.
+ *
+ * Sizes, modes, B and the band tables are those of the sections above; anything they refuse, or a NULL pointer, is PDWT_EINVAL and
+ * nothing is launched.  forward_adjoint reads the cotangent bands (left intact) and writes d_dst (B x Nr x Nc / nr x nc);
+ * inverse_adjoint reads d_src (left intact) and writes the bands.  d_coeffs is a HOST table.  Asynchronous on the library stream.
+ * Scratch of forward_adjoint, in elements: the whole-transform entries need pdwt_ext2db_adjoint_tmp_elems (never 0) /
+ * pdwt_ext1d_adjoint_tmp_elems (0 when all levels run in one launch: then d_tmp may be NULL); a level entry needs
+ * B * ((nr + 2F - 3) * (nc + 2F - 3) - nr * nc) / nr * (2F - 3) (the halo of the extended grid; may be NULL in mode 0).
+ * The 2-D whole transform loops the level kernels (PDWT_EXT2DB_LEVELS); the 1-D one returns PDWT_EXT1D_FUSED or PDWT_EXT1D_LEVELS,
+ * fused when pdwt_ext1d_fused says so and one more padded detail line per row fits the LDS of a workgroup.  Both forms give the same bits.
+ * ------------------------------------------------------------------------------------------- */
+long long pdwt_ext2db_adjoint_tmp_elems(int B, int Nr, int Nc, int hlen, int levels, int elem_size);
+int pdwt_ext2db_forward_adjoint_level_f32(float* d_dst, const float* d_a, const float* d_h, const float* d_v, const float* d_d, int B, int nr, int nc, int mode, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext2db_forward_adjoint_level_f64(double* d_dst, const double* d_a, const double* d_h, const double* d_v, const double* d_d, int B, int nr, int nc, int mode, const pdwt_filters_f64* f, double* d_tmp);
+int pdwt_ext2db_forward_adjoint_f32(float* d_dst, float* const* d_coeffs, int B, int Nr, int Nc, int levels, int mode, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext2db_forward_adjoint_f64(double* d_dst, double* const* d_coeffs, int B, int Nr, int Nc, int levels, int mode, const pdwt_filters_f64* f, double* d_tmp);
+int pdwt_ext2db_inverse_adjoint_f32(const float* d_src, float* const* d_coeffs, int B, int Nr, int Nc, int levels, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext2db_inverse_adjoint_f64(const double* d_src, double* const* d_coeffs, int B, int Nr, int Nc, int levels, const pdwt_filters_f64* f, double* d_tmp);
+long long pdwt_ext1d_adjoint_tmp_elems(int Nr, int Nc, int hlen, int levels, int elem_size);
+int pdwt_ext1d_forward_adjoint_level_f32(float* d_dst, const float* d_a, const float* d_d, int nr, int nc, int mode, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext1d_forward_adjoint_level_f64(double* d_dst, const double* d_a, const double* d_d, int nr, int nc, int mode, const pdwt_filters_f64* f, double* d_tmp);
+int pdwt_ext1d_forward_adjoint_f32(float* d_dst, float* const* d_coeffs, int nr, int nc, int levels, int mode, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext1d_forward_adjoint_f64(double* d_dst, double* const* d_coeffs, int nr, int nc, int levels, int mode, const pdwt_filters_f64* f, double* d_tmp);
+int pdwt_ext1d_inverse_adjoint_f32(const float* d_src, float* const* d_coeffs, int nr, int nc, int levels, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext1d_inverse_adjoint_f64(const double* d_src, double* const* d_coeffs, int nr, int nc, int levels, const pdwt_filters_f64* f, double* d_tmp);
+
+/* ---------------------------------------------------------------------------------------------
  * 3-D DWT with boundary modes (pdwt_amd/csrc/dwt_ext3d.hip; the class: BoundaryWavelets3D, include/wt_ext.h): the mathematics of
  * "2-D DWT with boundary modes" along x (the last axis), then y, then z of an nz x nr x nc volume -- pywt.wavedecn(vol, w, mode,
  * level).  One level gives eight bands of ((nz + F - 1) / 2) x ((nr + F - 1) / 2) x ((nc + F - 1) / 2), row-major; the modes are the

@@ -89,7 +89,7 @@ PLAIN_SYMBOLS = ["pdwt_device_count", "pdwt_set_device", "pdwt_get_device", "pdw
                  "pdwt_sum_scratch_doubles", "pdwt_sum_scratch_read", "pdwt_num_bands3d", "pdwt_band_size3d", "pdwt_tmp_elems3d",
                  "pdwt_num_bands_swt3d", "pdwt_band_size_swt3d", "pdwt_tmp_elems_swt3d", "pdwt_num_bands_ext", "pdwt_ext_band_shape",
                  "pdwt_num_bands_ext1d", "pdwt_ext1d_band_len", "pdwt_ext1d_fused", "pdwt_ext1d_tmp_elems",
-                 "pdwt_ext2db_fused", "pdwt_ext2db_tmp_elems",
+                 "pdwt_ext2db_fused", "pdwt_ext2db_tmp_elems", "pdwt_ext2db_adjoint_tmp_elems", "pdwt_ext1d_adjoint_tmp_elems",
                  "pdwt_num_bands_ext3d", "pdwt_ext3d_band_shape", "pdwt_ext3d_tmp_elems", "pdwt_ext3d_tmp_approx_offset",
                  "pdwt_wp1_geometry", "pdwt_wp1_fused", "pdwt_wp1_tmp_elems", "pdwt_wp1_frequency_order", "pdwt_wp1_state_table", "pdwt_memcpy2d",
                  "pdwt_wptb_geometry", "pdwt_wptb_fused", "pdwt_wptb_lds_bytes", "pdwt_wptb_tmp_elems", "pdwt_wptb_state_table", "pdwt_wptb_chunk_lists"]
@@ -104,6 +104,8 @@ TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coe
                   "ext1d_forward_level", "ext1d_inverse_level", "ext1d_forward", "ext1d_inverse",
                   "ext3d_forward_level", "ext3d_inverse_level",
                   "ext2db_forward_level", "ext2db_inverse_level", "ext2db_forward", "ext2db_inverse",
+                  "ext2db_forward_adjoint_level", "ext2db_forward_adjoint", "ext2db_inverse_adjoint",
+                  "ext1d_forward_adjoint_level", "ext1d_forward_adjoint", "ext1d_inverse_adjoint",
                   "wp1_forward_level", "wp1_inverse_level", "wp1_forward", "wp1_inverse", "wp1_moments", "wp1_thresh",
                   "wptb_forward", "wptb_inverse"] + DRIVERS + HAAR_DRIVERS)
 
@@ -256,6 +258,14 @@ def hip():
         getattr(L, "pdwt_ext2db_inverse_level_" + sfx).argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, C.POINTER(FT)]
         getattr(L, "pdwt_ext2db_forward_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, ci, C.POINTER(FT), vp]
         getattr(L, "pdwt_ext2db_inverse_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, C.POINTER(FT), vp]
+        # adjoints of the boundary-mode transforms: the forward adjoints take the output first, the cotangent bands like the inverse, and
+        # a scratch last; the inverse adjoints have the arguments of the forward entries without the mode
+        getattr(L, "pdwt_ext2db_forward_adjoint_level_" + sfx).argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, C.POINTER(FT), vp]
+        getattr(L, "pdwt_ext2db_forward_adjoint_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, ci, C.POINTER(FT), vp]
+        getattr(L, "pdwt_ext2db_inverse_adjoint_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, C.POINTER(FT), vp]
+        getattr(L, "pdwt_ext1d_forward_adjoint_level_" + sfx).argtypes = [vp, vp, vp, ci, ci, ci, C.POINTER(FT), vp]
+        getattr(L, "pdwt_ext1d_forward_adjoint_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, C.POINTER(FT), vp]
+        getattr(L, "pdwt_ext1d_inverse_adjoint_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, C.POINTER(FT), vp]
         # batched 1-D wavelet packets: one depth step (parents, children, nr, nnodes, n, [device list or NULL, count,] bank); the whole
         # tree (src or dst, HOST table of `levels` device pointers, nr, nc, levels, [device state table,] bank) -> 1 fused / 0 per level / < 0
         getattr(L, "pdwt_wp1_forward_level_" + sfx).argtypes = [vp, vp, ci, ci, ci, C.POINTER(FT)]
@@ -298,6 +308,10 @@ def hip():
     L.pdwt_ext2db_fused.argtypes = [ci, ci, ci, ci, ci]
     L.pdwt_ext2db_tmp_elems.restype = C.c_longlong
     L.pdwt_ext2db_tmp_elems.argtypes = [ci, ci, ci, ci, ci, ci]
+    L.pdwt_ext2db_adjoint_tmp_elems.restype = C.c_longlong
+    L.pdwt_ext2db_adjoint_tmp_elems.argtypes = [ci, ci, ci, ci, ci, ci]
+    L.pdwt_ext1d_adjoint_tmp_elems.restype = C.c_longlong
+    L.pdwt_ext1d_adjoint_tmp_elems.argtypes = [ci, ci, ci, ci, ci]
     _hip = L
     return L
 
