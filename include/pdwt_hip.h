@@ -666,6 +666,37 @@ int pdwt_ext3d_inverse_level_f32(float* d_dst, float* const* d_bands, int nz, in
 int pdwt_ext3d_inverse_level_f64(double* d_dst, double* const* d_bands, int nz, int nr, int nc, const pdwt_filters_f64* f, double* d_tmp);
 
 /* ---------------------------------------------------------------------------------------------
+ * Adjoints of the 3-D boundary-mode DWT (pdwt_amd/csrc/dwt_ext3d_adj.hip): the transposes W^T and S^T of the linear maps that
+ * pdwt_ext3d_forward_level_* (W, depends on the mode) and pdwt_ext3d_inverse_level_* (S) compute -- one level of a volume, in the
+ * notation of "Adjoints of the boundary-mode DWT".  The forward level runs x-y, then z; its adjoint runs z, then x-y:
+ *   along z, per column of each x-y quadrant q (cotangent stacks lo[q], hi[q] of hz = (nz + F - 1) / 2 planes)
+ *     u[s]    = sum_i lo[i] L[2i + 1 - s] + hi[i] H[2i + 1 - s]   s = 2 - F .. 2 hz - 1, planes outside 0 .. hz - 1 count as 0
+ *     Q[q][k] = sum of u[s] over the s that the mode maps to sample k, in ascending s (s = k in its place)
+ *   then the 2-D level adjoint of the section above on the nz planes, with A, H, V, D = Q[0 .. 3] (q = 2 * x band + y band).
+ * The sums are gathers in that fixed order (no atomics): a result does not depend on the tiling and two runs give the same bits.
+ * The adjoint of the inverse level is the forward level in mode 0 (zero) with the bank L' = IL reversed, H' = IH reversed:
+ * inverse_adjoint_level builds that bank, runs pdwt_ext3d_forward_level_* and returns its code.
+ *
+ * d_bands is the HOST array of 8 device pointers in the order aaa .. ddd of the level entries.  forward_adjoint_level reads the eight
+ * cotangent bands (left intact) and writes d_dst (nz x nr x nc), which must not overlap them; inverse_adjoint_level reads d_src (left
+ * intact, never the buffer of a band) and writes the eight bands.  d_tmp: pdwt_ext3d_adjoint_level_tmp_elems elements for either entry
+ * -- the four quadrant cotangents, 4 * nz * ((nr + F - 1) / 2) * ((nc + F - 1) / 2) padded to a multiple of 64, then the nz frames of
+ * the 2-D adjoint, nz * ((nr + 2F - 3) * (nc + 2F - 3) - nr * nc) at most; its contents afterwards are unspecified.
+ * The sizes are those of the level entries above and of the 2-D level adjoint with B = nz; anything they refuse, a NULL pointer (one of
+ * the eight included) or a bad mode is PDWT_EINVAL and nothing is launched (tmp_elems: PDWT_EINVAL).  Level entries only: the callers
+ * loop the levels, from the coarsest to the finest for forward_adjoint (the d_dst of a level is the aaa cotangent of the next finer
+ * one).  Asynchronous on the library stream; buffers need only be aligned to their element type.
+ * pdwt_ext3d_adjoint_z_run (no device needed): the longest run [z0, z1) of samples along z that no cell of the extension repeats in
+ * `mode`; a chunk of 16 samples from a multiple of 16 that lies inside it takes the path without a fold.
+ * ------------------------------------------------------------------------------------------- */
+long long pdwt_ext3d_adjoint_level_tmp_elems(int nz, int nr, int nc, int hlen);
+int pdwt_ext3d_adjoint_z_run(int nz, int hlen, int mode, int* z0, int* z1);
+int pdwt_ext3d_forward_adjoint_level_f32(float* d_dst, float* const* d_bands, int nz, int nr, int nc, int mode, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext3d_forward_adjoint_level_f64(double* d_dst, double* const* d_bands, int nz, int nr, int nc, int mode, const pdwt_filters_f64* f, double* d_tmp);
+int pdwt_ext3d_inverse_adjoint_level_f32(const float* d_src, float* const* d_bands, int nz, int nr, int nc, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext3d_inverse_adjoint_level_f64(const double* d_src, double* const* d_bands, int nz, int nr, int nc, const pdwt_filters_f64* f, double* d_tmp);
+
+/* ---------------------------------------------------------------------------------------------
  * Batched 1-D wavelet packets (pdwt_amd/csrc/wpt1d.hip; the class: WaveletPackets1D, include/wpt1d.h): the full binary tree of
  * every row of an Nr x Nc batch -- pywt.WaveletPacket(mode='periodization'), natural (Paley) order.  Depth l has 2^l nodes per row
  * of n_l = div2(n_{l-1}) samples (n_0 = Nc); node i has the children 2i (a) and 2i + 1 (d) of depth l + 1: the [A, D] bands of one

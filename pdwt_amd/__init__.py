@@ -13,6 +13,6 @@ from .swt3d import StationaryWavelets3D  # noqa: F401
 from .wpt import WaveletPacketBatch, WaveletPackets1D, WaveletPackets2D  # noqa: F401
 from .boundary import BoundaryImageBatch, BoundaryWavelets1D, BoundaryWavelets2D, BoundaryWavelets3D  # noqa: F401
 from . import functional  # noqa: F401
-from .functional import dwt1, dwt1_adjoint, dwt2, dwt2_adjoint, idwt1, idwt1_adjoint, idwt2, idwt2_adjoint  # noqa: F401
+from .functional import dwt1, dwt1_adjoint, dwt2, dwt2_adjoint, dwt3, dwt3_adjoint, idwt1, idwt1_adjoint, idwt2, idwt2_adjoint, idwt3, idwt3_adjoint  # noqa: F401
 
-__all__ = ["Wavelets", "Wavelets3D", "StationaryWavelets3D", "WaveletPackets2D", "WaveletPackets1D", "WaveletPacketBatch", "BoundaryWavelets2D", "BoundaryWavelets1D", "BoundaryWavelets3D", "BoundaryImageBatch", "ImageBatch", "DeviceArray", "functional", "dwt2", "idwt2", "dwt1", "idwt1", "dwt2_adjoint", "idwt2_adjoint", "dwt1_adjoint", "idwt1_adjoint", "Info", "hip", "host", "require_gpu"]
+__all__ = ["Wavelets", "Wavelets3D", "StationaryWavelets3D", "WaveletPackets2D", "WaveletPackets1D", "WaveletPacketBatch", "BoundaryWavelets2D", "BoundaryWavelets1D", "BoundaryWavelets3D", "BoundaryImageBatch", "ImageBatch", "DeviceArray", "functional", "dwt2", "idwt2", "dwt1", "idwt1", "dwt2_adjoint", "idwt2_adjoint", "dwt1_adjoint", "idwt1_adjoint", "dwt3", "idwt3", "dwt3_adjoint", "idwt3_adjoint", "Info", "hip", "host", "require_gpu"]

@@ -193,19 +193,7 @@ static int run_ext3_z(int hlen, bool fwd, const Ext3ZJob<T>& zj, const Taps2<T>&
     return with_filter_length(hlen, [&](auto hl) { return launch_ext3_z<T, decltype(hl)::value>(fwd, zj, taps); });
 }
 
-// what both directions refuse: the limits of the volume transforms (vol_sizes_ok: nz a grid dimension, a plane indexed with 32 bits)
-// and of the 2-D level (a bad bank length, an axis shorter than hlen - 1, more rows of tiles than a grid dimension)
-static bool ext3_level_ok(int nz, int nr, int nc, int hlen)
-{
-    if (hlen < 2 || hlen > PDWT_MAX_FILTER_WIDTH || (hlen & 1)) return false;
-    if (nz < 1 || nr < 1 || nc < 1 || nz < hlen - 1 || nr < hlen - 1 || nc < hlen - 1) return false;
-    if (nz > 65535 || nr > (1 << 30) || nc > (1 << 30)) return false;
-    if ((unsigned long long)nr * (unsigned long long)nc >= (1ull << 31)) return false;  // (the expanded plane is no larger: n >= hlen - 1)
-    return idiv_up(ext_half(nr, hlen), X3FY) <= 65535 && idiv_up(nr, X3IY) <= 65535;
-}
-
-// band k (aaa, aad, ada, add, daa, dad, dda, ddd: bits z y x) of quadrant q (2 * x band + y band) and z band zb
-static inline int ext3_band(int q, int zb) { return 4 * zb + 2 * (q & 1) + (q >> 1); }
+// (ext3_level_ok, what both directions refuse, and ext3_band, the band of a quadrant: dwt_ext3d_xy.hpp)
 
 template <typename T>
 static int ext3_forward_level(const T* src, T* const* b, int nz, int nr, int nc, int mode, const typename FiltersOf<T>::type* f, T* tmp)

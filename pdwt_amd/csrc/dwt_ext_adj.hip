@@ -189,7 +189,8 @@ __global__ __launch_bounds__(kExt1dThreads) void k_ext1d_adj_fused(T* __restrict
 }
 
 // ---- geometry (host, no device) ---------------------------------------------------------------------------------------------------
-static bool adj2_level_ok(long long B, int nr, int nc, int hlen)
+// (external linkage: the 3-D adjoint, dwt_ext3d_adj.hip, refuses what this refuses with B = nz)
+bool adj2_level_ok(long long B, int nr, int nc, int hlen)
 {
     if (hlen < 2 || hlen > PDWT_MAX_FILTER_WIDTH || (hlen & 1)) return false;
     if (B < 1 || B > kAdjMaxBatch) return false;
@@ -251,8 +252,9 @@ static int launch_adj_syn(const AdjJob<T>& job, int B, const Taps2<T>& taps)
     return PDWT_OK;
 }
 
+// (external linkage: dwt_ext3d_adj.hip runs it on the nz planes of a volume)
 template <typename T>
-static int adj2_forward_level(T* dst, const T* a, const T* h, const T* v, const T* d, int B, int nr, int nc, int mode, const typename FiltersOf<T>::type* f, T* tmp)
+int adj2_forward_level(T* dst, const T* a, const T* h, const T* v, const T* d, int B, int nr, int nc, int mode, const typename FiltersOf<T>::type* f, T* tmp)
 {
     if (!dst || !a || !h || !v || !d || !f || mode < 0 || mode >= EXT_NUM_MODES || !adj2_level_ok(B, nr, nc, f->hlen)) return PDWT_EINVAL;
     const int hlen = f->hlen;
@@ -269,6 +271,9 @@ static int adj2_forward_level(T* dst, const T* a, const T* h, const T* v, const 
     PDWT_HIP_TRY(hipGetLastError());
     return PDWT_OK;
 }
+
+template int adj2_forward_level<float>(float*, const float*, const float*, const float*, const float*, int, int, int, int, const pdwt_filters_f32*, float*);
+template int adj2_forward_level<double>(double*, const double*, const double*, const double*, const double*, int, int, int, int, const pdwt_filters_f64*, double*);
 
 template <typename T>
 static int adj2_forward(T* dst, T* const* c, int B, int Nr, int Nc, int levels, int mode, const typename FiltersOf<T>::type* f, T* tmp)
@@ -348,16 +353,6 @@ static int adj1_forward(T* dst, T* const* c, int nr, int nc, int levels, int mod
         if (const int rc = adj1_forward_level<T>(out, a, b.p[l], nr, b.n[l - 1], mode, f, tmp); rc != PDWT_OK) return rc;
     }
     return PDWT_EXT1D_LEVELS;
-}
-
-// the bank whose forward transform in mode zero is the adjoint of the inverse: L' = reversed IL, H' = reversed IH
-template <typename T>
-static bool adj_inverse_bank(typename FiltersOf<T>::type& g, const typename FiltersOf<T>::type* f)
-{
-    if (!f || f->hlen < 2 || f->hlen > PDWT_MAX_FILTER_WIDTH || (f->hlen & 1)) return false;
-    g = *f;
-    for (int i = 0; i < f->hlen; i++) g.L[i] = f->IL[f->hlen - 1 - i], g.H[i] = f->IH[f->hlen - 1 - i];
-    return true;
 }
 
 }  // namespace pdwt

@@ -233,4 +233,22 @@ __host__ __device__ __forceinline__ bool adj_fold_sample(T* __restrict__ img, co
     return true;
 }
 
+// ---- what dwt_ext_adj.hip shares with the 3-D adjoint (dwt_ext3d_adj.hip) --------------------------------------------------------------
+// what a 2-D level adjoint on B images refuses
+bool adj2_level_ok(long long B, int nr, int nc, int hlen);
+// one level of the 2-D adjoint of the forward transform on B images: (a, h, v, d) cotangent stacks (B, hr, hc) -> dst (B, nr, nc); tmp: B
+// frames of adj_frame_elems (may be NULL in mode zero).  Defined and instantiated for float and double in dwt_ext_adj.hip.
+template <typename T>
+int adj2_forward_level(T* dst, const T* a, const T* h, const T* v, const T* d, int B, int nr, int nc, int mode, const typename FiltersOf<T>::type* f, T* tmp);
+
+// the bank whose forward transform in mode zero is the adjoint of the inverse: L' = reversed IL, H' = reversed IH
+template <typename T>
+inline bool adj_inverse_bank(typename FiltersOf<T>::type& g, const typename FiltersOf<T>::type* f)
+{
+    if (!f || f->hlen < 2 || f->hlen > PDWT_MAX_FILTER_WIDTH || (f->hlen & 1)) return false;
+    g = *f;
+    for (int i = 0; i < f->hlen; i++) g.L[i] = f->IL[f->hlen - 1 - i], g.H[i] = f->IH[f->hlen - 1 - i];
+    return true;
+}
+
 }  // namespace pdwt

@@ -1,14 +1,16 @@
 """Differentiable boundary-mode DWT for torch device tensors: a stateless layer over the C-ABI drivers of include/pdwt_hip.h
-("Batched 2-D / 1-D DWT with boundary modes" and "Adjoints of the boundary-mode DWT").
+("Batched 2-D / 1-D DWT with boundary modes", "3-D DWT with boundary modes" and the two "Adjoints ..." sections).
 
     bands = dwt2(x, "db2", levels=2, mode="symmetric")   # x: (..., Nr, Nc) -> [A_L, H1, V1, D1, ..., H_L, V_L, D_L], each (..., nr_l, nc_l)
     x     = idwt2(bands, (Nr, Nc), "db2")
     bands = dwt1(x, "db4", levels=3, mode="periodic")    # x: (..., n) along the last axis -> [A_L, D_1, ..., D_L]
     x     = idwt1(bands, n, "db4")
+    bands = dwt3(x, "db2", levels=2, mode="symmetric")   # x: (..., Nz, Nr, Nc) -> [A_L, 7 details of level L, ..., 7 details of level 1]
+    x     = idwt3(bands, (Nz, Nr, Nc), "db2")            # (COARSEST level first, unlike dwt2: the table of BoundaryWavelets3D)
 
-The four transforms are ``torch.autograd.Function``s (once differentiable): they accept ``requires_grad`` inputs and take part in a graph;
+The six transforms are ``torch.autograd.Function``s (once differentiable): they accept ``requires_grad`` inputs and take part in a graph;
 their backward is the matching adjoint operator, which is also exposed bare: ``dwt2_adjoint``, ``idwt2_adjoint``, ``dwt1_adjoint``,
-``idwt1_adjoint``.  With a signal extension the adjoint of the forward transform is not the inverse.
+``idwt1_adjoint``, ``dwt3_adjoint``, ``idwt3_adjoint``.  With a signal extension the adjoint of the forward transform is not the inverse.
 
 Tensors must be contiguous float32 / float64 tensors on the GPU (``TypeError`` otherwise); outputs and scratch are torch allocations.
 Nothing is clamped: ``levels < 1``, a level whose axis is shorter than ``hlen - 1``, an unknown mode or wavelet, or a band list of the
@@ -23,8 +25,11 @@ from .wavelets import _sync_producer
 MODES = ("zero", "constant", "symmetric", "reflect", "periodic")
 MAX_LEVELS = 32
 MAX_BATCH = 65535
+MAX_LEVELS_3D = 13
+KEYS_3D = ("aad", "ada", "add", "daa", "dad", "dda", "ddd")  # a level's details in table order (first letter: the z axis, a = low pass)
 
-__all__ = ["dwt2", "idwt2", "dwt1", "idwt1", "dwt2_adjoint", "idwt2_adjoint", "dwt1_adjoint", "idwt1_adjoint", "MODES"]
+__all__ = ["dwt2", "idwt2", "dwt1", "idwt1", "dwt3", "idwt3", "dwt2_adjoint", "idwt2_adjoint", "dwt1_adjoint", "idwt1_adjoint", "dwt3_adjoint",
+           "idwt3_adjoint", "MODES"]
 
 _banks = {}
 _fn = None
@@ -67,9 +72,9 @@ def _mode(mode):
     return MODES.index(mode)
 
 
-def _levels(levels):
-    if int(levels) != levels or not 1 <= int(levels) <= MAX_LEVELS:
-        raise ValueError("levels must be 1 .. %d, not %r" % (MAX_LEVELS, levels))
+def _levels(levels, most=MAX_LEVELS):
+    if int(levels) != levels or not 1 <= int(levels) <= most:
+        raise ValueError("levels must be 1 .. %d, not %r" % (most, levels))
     return int(levels)
 
 
@@ -92,7 +97,7 @@ def _count(lead, limit, what):
     return b
 
 
-def _band_list(bands, per_level):
+def _band_list(bands, per_level, most=MAX_LEVELS):
     torch = _torch()
     if not isinstance(bands, (list, tuple)) or len(bands) < per_level + 1 or (len(bands) - 1) % per_level:
         raise ValueError("a band list of %d * levels + 1 tensors is required" % per_level)
@@ -100,7 +105,7 @@ def _band_list(bands, per_level):
     for b in bands[1:]:
         if _sfx(b) != sfx or b.device != bands[0].device:
             raise ValueError("the bands must share dtype and device")
-    return list(bands), sfx, _levels((len(bands) - 1) // per_level)
+    return list(bands), sfx, _levels((len(bands) - 1) // per_level, most)
 
 
 def _check_shapes(bands, lead, shapes):
@@ -242,6 +247,114 @@ def _idwt1(bands, n, wname, mode=None):
     return out
 
 
+# ---- 3-D: the level entries, one volume per call (leading axes loop; the levels loop here) --------------------------------------------
+def _shape3(shape):
+    if len(shape) != 3 or any(int(v) != v or int(v) < 1 for v in shape):
+        raise ValueError("shape must be (Nz, Nr, Nc), not %r" % (tuple(shape),))
+    return tuple(int(v) for v in shape)
+
+
+def _geom3(shape3, hlen, levels):
+    """([(nz_l, nr_l, nc_l) for l = 0 .. levels], scratch elements): every level is one the level entries take"""
+    axes = [_axis_lengths(n, hlen, levels, what) for n, what in zip(shape3, ("z", "row", "column"))]
+    shapes = [tuple(a[l] for a in axes) for l in range(levels + 1)]
+    L = N.hip()
+    tmp = 0
+    for l in range(levels):
+        e = L.pdwt_ext3d_adjoint_level_tmp_elems(shapes[l][0], shapes[l][1], shapes[l][2], hlen)
+        if e < 0:
+            raise ValueError("level %d: a %d x %d x %d volume is a size the level drivers refuse" % ((l + 1,) + shapes[l]))
+        tmp = max(tmp, e)
+    return shapes, tmp
+
+
+def _table_shapes3(shapes, levels):
+    return [shapes[levels]] + [shapes[l] for l in range(levels, 0, -1) for _ in range(7)]
+
+
+class _Calls3:
+    """the calls of one operator: the device check once, then per call the producer / consumer ordering of _run"""
+
+    def __init__(self, sfx, like, tmp_elems):
+        torch = _torch()
+        self.L = N.hip()
+        if like.device.index is not None and like.device.index != self.L.pdwt_get_device():
+            raise ValueError("the tensors live on device %d, the library runs on device %d (pdwt_set_device)" % (like.device.index, self.L.pdwt_get_device()))
+        self.sfx, self.es = sfx, like.element_size()
+        self.tmp = torch.empty(int(tmp_elems), dtype=like.dtype, device=like.device)
+
+    def scratch(self, like, shapes):
+        return [like.new_empty(s) for s in shapes]
+
+    def ptr(self, t, volume, shape):
+        return t.data_ptr() + volume * shape[0] * shape[1] * shape[2] * self.es
+
+    def __call__(self, name, *args):
+        L = self.L
+        _sync_producer()
+        rc = getattr(L, "pdwt_%s_%s" % (name, self.sfx))(*args, C.c_void_p(self.tmp.data_ptr()))
+        if rc < 0:
+            raise RuntimeError("pdwt_%s_%s failed (%d): %s" % (name, self.sfx, rc, (L.pdwt_last_error_string() or b"").decode()))
+        if L.pdwt_sync() != 0:
+            raise RuntimeError("pdwt_sync failed: %s" % (L.pdwt_last_error_string() or b"").decode())
+
+
+def _dwt3(x, wname, levels, mode, adjoint_of_inverse=False):
+    sfx = _sfx(x)
+    if x.dim() < 3:
+        raise ValueError("a tensor of shape (..., Nz, Nr, Nc) is required")
+    levels, f = _levels(levels, MAX_LEVELS_3D), _bank(wname, sfx)
+    m = 0 if adjoint_of_inverse else _mode(mode)
+    lead, shape = tuple(x.shape[:-3]), _shape3(x.shape[-3:])
+    shapes, tmp = _geom3(shape, f.hlen, levels)
+    V = _count(lead, (1 << 31) - 1, "volumes")
+    tshapes = _table_shapes3(shapes, levels)
+    bands = [x.new_empty(lead + s) for s in tshapes]
+    run = _Calls3(sfx, x, tmp)
+    approx = run.scratch(x, shapes[1:levels])  # aaa of the levels 1 .. levels - 1 of one volume: never x, never a band
+    for v in range(V):
+        for l in range(1, levels + 1):
+            src = run.ptr(x, v, shape) if l == 1 else approx[l - 2].data_ptr()
+            aaa = run.ptr(bands[0], v, shapes[levels]) if l == levels else approx[l - 1].data_ptr()
+            k0 = 1 + 7 * (levels - l)
+            tab = (C.c_void_p * 8)(aaa, *[run.ptr(b, v, shapes[l]) for b in bands[k0:k0 + 7]])
+            nz, nr, nc = shapes[l - 1]
+            if adjoint_of_inverse:
+                run("ext3d_inverse_adjoint_level", C.c_void_p(src), tab, nz, nr, nc, C.byref(f))
+            else:
+                run("ext3d_forward_level", C.c_void_p(src), tab, nz, nr, nc, m, C.byref(f))
+    return bands
+
+
+def _idwt3(bands, shape, wname, mode=None):
+    """mode None: the inverse; a mode: the adjoint of the forward transform.  Coarse to fine: the output of a level is aaa of the next"""
+    bands, sfx, levels = _band_list(bands, 7, MAX_LEVELS_3D)
+    f = _bank(wname, sfx)
+    m = None if mode is None else _mode(mode)
+    shape = _shape3(shape)
+    shapes, tmp = _geom3(shape, f.hlen, levels)
+    if bands[0].dim() < 3:
+        raise ValueError("bands of shape (..., nz, nr, nc) are required")
+    lead = tuple(bands[0].shape[:-3])
+    _check_shapes(bands, lead, _table_shapes3(shapes, levels))
+    V = _count(lead, (1 << 31) - 1, "volumes")
+    out = bands[0].new_empty(lead + shape)
+    run = _Calls3(sfx, out, tmp)
+    approx = run.scratch(out, shapes[1:levels])
+    for v in range(V):
+        for l in range(levels, 0, -1):
+            aaa = run.ptr(bands[0], v, shapes[levels]) if l == levels else approx[l - 1].data_ptr()
+            dst = run.ptr(out, v, shape) if l == 1 else approx[l - 2].data_ptr()
+            k0 = 1 + 7 * (levels - l)
+            tab = (C.c_void_p * 8)(aaa, *[run.ptr(b, v, shapes[l]) for b in bands[k0:k0 + 7]])
+            nz, nr, nc = shapes[l - 1]
+            if m is None:
+                run("ext3d_inverse_level", C.c_void_p(dst), tab, nz, nr, nc, C.byref(f))
+            else:
+                run("ext3d_forward_adjoint_level", C.c_void_p(dst), tab, nz, nr, nc, m, C.byref(f))
+    return out
+
+
 # ---- the bare adjoints -----------------------------------------------------------------------------------------------------------
 def dwt2_adjoint(bands, shape, wname, mode="symmetric"):
     """W^T: the cotangents of ``dwt2``'s band list -> a tensor of shape (..., Nr, Nc); ``shape`` = (Nr, Nc)"""
@@ -263,6 +376,17 @@ def idwt1_adjoint(x, wname, levels=1):
     return _dwt1(x.detach(), wname, levels, None, adjoint_of_inverse=True)
 
 
+def dwt3_adjoint(bands, shape, wname, mode="symmetric"):
+    """W^T: the cotangents of ``dwt3``'s band table -> a tensor of shape (..., Nz, Nr, Nc); ``shape`` = (Nz, Nr, Nc)"""
+    return _idwt3([b.detach() for b in _tensors(bands)], shape, wname, mode)
+
+
+def idwt3_adjoint(x, wname, levels=1):
+    """S^T: the cotangent of ``idwt3``'s volume -> the band table of ``levels`` levels (the order of ``dwt3``)"""
+    _sfx(x)
+    return _dwt3(x.detach(), wname, levels, None, adjoint_of_inverse=True)
+
+
 def _tensors(bands):
     if not isinstance(bands, (list, tuple)):
         raise ValueError("a list of band tensors is required")
@@ -273,7 +397,7 @@ def _tensors(bands):
 
 # ---- autograd ----------------------------------------------------------------------------------------------------------------------
 def _functions():
-    """the four torch.autograd.Functions, made on first use (importing pdwt_amd does not import torch)"""
+    """the six torch.autograd.Functions, made on first use (importing pdwt_amd does not import torch)"""
     global _fn
     if _fn is not None:
         return _fn
@@ -328,7 +452,31 @@ def _functions():
             wname, levels = ctx.meta
             return (None, None) + tuple(_dwt1(grad.contiguous(), wname, levels, None, adjoint_of_inverse=True))
 
-    _fn = {"dwt2": DWT2, "idwt2": IDWT2, "dwt1": DWT1, "idwt1": IDWT1}
+    class DWT3(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, x, wname, levels, mode):
+            ctx.meta = (tuple(x.shape[-3:]), wname, mode)
+            return tuple(_dwt3(x.detach(), wname, levels, mode))
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, *grads):
+            shape, wname, mode = ctx.meta
+            return _idwt3([g.contiguous() for g in grads], shape, wname, mode), None, None, None
+
+    class IDWT3(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, shape, wname, *bands):
+            ctx.meta = (wname, (len(bands) - 1) // 7)
+            return _idwt3([b.detach() for b in bands], shape, wname)
+
+        @staticmethod
+        @once_differentiable
+        def backward(ctx, grad):
+            wname, levels = ctx.meta
+            return (None, None) + tuple(_dwt3(grad.contiguous(), wname, levels, None, adjoint_of_inverse=True))
+
+    _fn = {"dwt2": DWT2, "idwt2": IDWT2, "dwt1": DWT1, "idwt1": IDWT1, "dwt3": DWT3, "idwt3": IDWT3}
     return _fn
 
 
@@ -352,3 +500,17 @@ def dwt1(x, wname, levels=1, mode="symmetric"):
 def idwt1(bands, n, wname):
     """the (..., n) tensor from the band list of ``dwt1``"""
     return _functions()["idwt1"].apply(n, wname, *_tensors(bands))
+
+
+def dwt3(x, wname, levels=1, mode="symmetric"):
+    """[A_L, the 7 details of level L, ..., the 7 details of level 1] of x (..., Nz, Nr, Nc), a level's details in the order aad, ada, add,
+    daa, dad, dda, ddd (first letter: the z axis): the band table of ``BoundaryWavelets3D`` and the flattened ``pywt.wavedecn(x, wname, mode,
+    levels, axes=(-3, -2, -1))``.  The COARSEST level comes first -- unlike ``dwt2``, whose details run from level 1 up.  ``levels`` is
+    1 .. 13 and is not clamped."""
+    _sfx(x)
+    return list(_functions()["dwt3"].apply(x, wname, levels, mode))
+
+
+def idwt3(bands, shape, wname):
+    """the (..., Nz, Nr, Nc) tensor of ``shape`` = (Nz, Nr, Nc) from the band table of ``dwt3`` (no mode: the inverse needs no extension)"""
+    return _functions()["idwt3"].apply(tuple(shape), wname, *_tensors(bands))
