@@ -23,7 +23,7 @@
 #ifndef WPT_H
 #define WPT_H
 
-#include "wt.h"
+#include "wpt_tree.h"
 
 #define WPT_MAX_LEVELS 7
 
@@ -33,24 +33,18 @@ struct w_info_wpt {
     int hlen;
 };
 
-class WaveletPackets {
+/* d_image, d_nodes (depths 0 .. WPT_MAX_LEVELS are used), wname and state are members of the base, with the methods that are not
+ * declared here: forward, inverse, set_image, node_shape, get_level, best_basis, set_basis, basis_size, get_basis, soft_threshold,
+ * hard_threshold, node_stats, estimate_sigma (include/wpt_tree.h).
+ * node_shape(depth, &nr, &nc) (valid unless W_CREATION_ERROR): nodes of a depth = 4^depth; elements of one node, 0 for a bad depth. */
+class WaveletPackets : public PacketTree {
   public:
-    DTYPE* d_image;                      /* device: image / reconstruction = the node of depth 0 */
-    DTYPE* d_nodes[WPT_MAX_LEVELS + 1];  /* device: the node array of each depth ([0] = d_image) */
-    char wname[128];
     w_info_wpt winfos;
-    w_state state;
 
     WaveletPackets(DTYPE* img, int Nr, int Nc, const char* wname, int levels, int memisonhost = 1);
-    ~WaveletPackets();
 
-    void forward();
-    void inverse();
-    int get_image(DTYPE* img);
-    void set_image(DTYPE* img, int mem_is_on_device = 0);
+    int get_image(DTYPE* img) { return (int)tree_get_image(img); }
 
-    /* geometry (valid unless W_CREATION_ERROR): nodes of a depth = 4^depth; elements of one node, 0 for a bad depth */
-    long long node_shape(int depth, int* nr, int* nc) const;
     /* the depth an instance of this size gets (levels < 1 asks for 1; clamped to ilog2(min(Nr, Nc) / (hlen - 1)) and WPT_MAX_LEVELS;
      * 0 = too small or a bad size) and, in nr / nc when given, the node shape of depth 0 .. that depth.  What the constructor uses. */
     static int geometry(int Nr, int Nc, int hlen, int levels, int* nr, int* nc);
@@ -59,35 +53,22 @@ class WaveletPackets {
 
     /* copy out / in: elements copied, 0 when refused.  get_level copies all 4^depth nodes of a depth.  set_node needs the tree
      * of a forward() (W_FORWARD / W_THRESHOLD; refused otherwise, also after inverse()) and gives W_THRESHOLD. */
-    int get_node(DTYPE* out, int depth, int idx);
-    long long get_level(DTYPE* out, int depth);
-    int set_node(DTYPE* in, int depth, int idx, int mem_is_on_device = 0);
-    intptr_t node_int_ptr(int depth, int idx);
+    int get_node(DTYPE* out, int depth, int idx) { return (int)tree_get_node(out, depth, idx); }
+    int set_node(DTYPE* in, int depth, int idx, int mem_is_on_device = 0) { return (int)tree_set_node(in, depth, idx, mem_is_on_device); }
+    intptr_t node_int_ptr(int depth, int idx) { return tree_node_ptr(depth, idx, NULL); }
 
     /* additive costs of all 4^depth nodes of a depth (0 .. L; depth 0 = the image) in one launch, in double on the host:
      * kind 0 "l1" = sum |c|, kind 1 "shannon" = -sum c^2 ln c^2 (zero terms skipped).  PDWT_OK or a negative code. */
     int node_costs(int depth, int kind, double* out);
-    /* bottom-up best basis on the host: a parent is kept when its cost is <= the sum of its children's best costs.  Installs the
-     * basis; returns the number of its nodes (see get_basis), or a negative code when refused. */
-    int best_basis(int kind);
-    /* install a basis given as n (depth, idx) pairs; PDWT_EINVAL unless they partition the tree (overlap, gap, bad index) */
-    int set_basis(const int* depth, const int* idx, int n);
-    int basis_size() const;
-    int get_basis(int* depth, int* idx) const; /* sorted by (depth, idx); returns the count */
-
-    /* on the nodes of the current basis; the all-"a" node only when do_thresh_appcoeffs; one launch per depth that holds basis nodes */
-    void soft_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
-    void hard_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
-    double norm1(); /* sum |c| over the basis, in double; -1 when refused */
-    /* n, sum |c|, sum c^2, max |c| of every node of a depth (out: 4^depth entries; median_abs NaN) */
-    int node_stats(int depth, w_band_stats* out);
-    double estimate_sigma(); /* median |node "d"| / 0.6744897501960817; -1 when refused */
-
-  private:
-    void* priv_; /* bank, device, basis flags, device tables */
-    void threshold(int op, DTYPE beta, int do_thresh_appcoeffs);
-    WaveletPackets(const WaveletPackets&);
-    WaveletPackets& operator=(const WaveletPackets&);
+    /* best_basis(kind): bottom-up best basis on the host: a parent is kept when its cost is <= the sum of its children's best costs.
+     * Installs the basis; returns the number of its nodes (see get_basis), or a negative code when refused.
+     * set_basis(depth, idx, n): install a basis given as n (depth, idx) pairs; PDWT_EINVAL unless they partition the tree (overlap, gap,
+     * bad index).  get_basis(depth, idx): sorted by (depth, idx); returns the count.
+     * soft_threshold / hard_threshold(beta, do_thresh_appcoeffs = 0): on the nodes of the current basis; the all-"a" node only when
+     * do_thresh_appcoeffs; one launch per depth that holds basis nodes.
+     * node_stats(depth, out): n, sum |c|, sum c^2, max |c| of every node of a depth (out: 4^depth entries; median_abs NaN).
+     * estimate_sigma(): median |node "d"| / 0.6744897501960817; -1 when refused. */
+    double norm1() { return tree_norm1(); } /* sum |c| over the basis, in double; -1 when refused */
 };
 
 #endif

@@ -25,7 +25,7 @@
 #ifndef WPT1D_H
 #define WPT1D_H
 
-#include "wt.h"
+#include "wpt_tree.h"
 
 #define WPT1D_MAX_LEVELS 12
 
@@ -35,25 +35,20 @@ struct w_info_wpt1 {
     int hlen;
 };
 
-class WaveletPackets1D {
+/* d_image, d_nodes, wname and state are members of the base, with the methods that are not declared here: forward, inverse, set_image,
+ * node_shape, get_level, best_basis, set_basis, basis_size, get_basis, soft_threshold, hard_threshold, node_stats, estimate_sigma
+ * (include/wpt_tree.h); they mean what they mean in WaveletPackets (include/wpt.h), with these differences:
+ * node_shape(depth, &nr, &n): elements of one node (Nr * n_l) with its shape, 0 for a bad depth.  get_level copies the (Nr, 2^l, n_l)
+ * allocation.  node_stats: of every node of a depth over all rows (out: 2^depth entries; median_abs NaN). */
+class WaveletPackets1D : public PacketTree {
   public:
-    DTYPE* d_image;                        /* device: the batch / reconstruction = depth 0 */
-    DTYPE* d_nodes[WPT1D_MAX_LEVELS + 1];  /* device: the allocation of each depth ([0] = d_image) */
-    char wname[128];
     w_info_wpt1 winfos;
-    w_state state;
 
     WaveletPackets1D(DTYPE* rows, int Nr, int Nc, const char* wname, int levels, int memisonhost = 1);
-    ~WaveletPackets1D();
 
-    void forward();
-    void inverse();
-    int get_image(DTYPE* rows);
-    void set_image(DTYPE* rows, int mem_is_on_device = 0);
-    int fused() const; /* 1: the whole tree of a row is one launch; 0: one launch per depth */
+    int get_image(DTYPE* rows) { return (int)tree_get_image(rows); }
+    int fused() const { return tree_fused(); } /* 1: the whole tree of a row is one launch; 0: one launch per depth */
 
-    /* geometry (valid unless W_CREATION_ERROR): elements of one node (Nr * n_l) with its shape in nr / n; 0 for a bad depth */
-    long long node_shape(int depth, int* nr, int* n) const;
     /* the depth an instance gets (levels < 1 asks for 1; 0 = too small or a bad size) and, in n when given, n_0 .. n_L */
     static int geometry(int Nc, int hlen, int levels, int* n);
     /* index of the node a path over "ad" names ("" = the batch), its depth in *depth; -1 for a bad letter or a path deeper than 12 */
@@ -61,36 +56,18 @@ class WaveletPackets1D {
     /* out[r] = r ^ (r >> 1): the natural index of the node of frequency rank r; the count 2^depth, or 0 for a bad depth */
     static int frequency_order(int depth, int* out);
 
-    /* copy out / in (a node is Nr x n_l, dense on the host): elements copied, 0 when refused.  get_level copies the (Nr, 2^l, n_l)
-     * allocation.  set_node needs the tree of a forward() (W_FORWARD / W_THRESHOLD) and gives W_THRESHOLD. */
-    int get_node(DTYPE* out, int depth, int idx);
-    long long get_level(DTYPE* out, int depth);
-    int set_node(DTYPE* in, int depth, int idx, int mem_is_on_device = 0);
+    /* copy out / in (a node is Nr x n_l, dense on the host): elements copied, 0 when refused.  set_node needs the tree of a forward()
+     * (W_FORWARD / W_THRESHOLD) and gives W_THRESHOLD. */
+    int get_node(DTYPE* out, int depth, int idx) { return (int)tree_get_node(out, depth, idx); }
+    int set_node(DTYPE* in, int depth, int idx, int mem_is_on_device = 0) { return (int)tree_set_node(in, depth, idx, mem_is_on_device); }
     /* device address of row 0 of a node; consecutive rows are *pitch ELEMENTS apart (2^depth * n_depth) */
-    intptr_t node_int_ptr(int depth, int idx, long long* pitch);
+    intptr_t node_int_ptr(int depth, int idx, long long* pitch) { return tree_node_ptr(depth, idx, pitch); }
 
     /* additive costs of all 2^depth nodes of a depth (0 .. L) in one launch, in double on the host, summed over the rows in row
      * order: kind 0 "l1" = sum |c|, kind 1 "shannon" = -sum c^2 ln c^2 (zero terms skipped).  per_row, when given, receives the
      * Nr * 2^depth costs of every (row, node).  PDWT_OK or a negative code. */
     int node_costs(int depth, int kind, double* out, double* per_row = 0);
-    int best_basis(int kind);
-    int set_basis(const int* depth, const int* idx, int n);
-    int basis_size() const;
-    int get_basis(int* depth, int* idx) const; /* sorted by (depth, idx); returns the count */
-
-    /* on the nodes of the current basis; the all-"a" node only when do_thresh_appcoeffs; one launch per depth that holds basis nodes */
-    void soft_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
-    void hard_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
-    double norm1(); /* sum |c| over the basis, in double; -1 when refused */
-    /* n, sum |c|, sum c^2, max |c| of every node of a depth over all rows (out: 2^depth entries; median_abs NaN) */
-    int node_stats(int depth, w_band_stats* out);
-    double estimate_sigma(); /* median |node "d"| / 0.6744897501960817; -1 when refused */
-
-  private:
-    void* priv_; /* bank, device, basis flags, device tables */
-    void threshold(int op, DTYPE beta, int do_thresh_appcoeffs);
-    WaveletPackets1D(const WaveletPackets1D&);
-    WaveletPackets1D& operator=(const WaveletPackets1D&);
+    double norm1() { return tree_norm1(); } /* sum |c| over the basis, in double; -1 when refused */
 };
 
 #endif

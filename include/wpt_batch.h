@@ -29,57 +29,37 @@ struct w_info_wptb {
     int hlen;
 };
 
-class WaveletPacketsImages {
+/* d_image, d_nodes (depths 0 .. WPT_MAX_LEVELS are used), wname and state are members of the base, with the methods that are not
+ * declared here: forward, inverse, set_image (all B images), node_shape (of one node of one image), get_level (the whole depth
+ * (B, 4^depth, nr, nc)), best_basis (over the costs summed over the images), set_basis, basis_size, get_basis, soft_threshold,
+ * hard_threshold (in every image), node_stats (per (image, node): B * 4^depth entries, image-major; median_abs NaN), estimate_sigma
+ * (pooled: median |node "d"| over all images / 0.6744897501960817) (include/wpt_tree.h; as WaveletPackets, include/wpt.h). */
+class WaveletPacketsImages : public PacketTree {
   public:
-    DTYPE* d_image;                      /* device: the B images / reconstructions = the nodes of depth 0 */
-    DTYPE* d_nodes[WPT_MAX_LEVELS + 1];  /* device: the allocation of each depth ([0] = d_image) */
-    char wname[128];
     w_info_wptb winfos;
-    w_state state;
 
     WaveletPacketsImages(DTYPE* imgs, int B, int Nr, int Nc, const char* wname, int levels, int memisonhost = 1, int allow_fused = 1);
-    ~WaveletPacketsImages();
 
-    void forward();
-    void inverse();
-    long long get_image(DTYPE* imgs);                         /* all B images; elements copied */
-    void set_image(DTYPE* imgs, int mem_is_on_device = 0);    /* all B images */
-    int fused() const;                                        /* 1: one launch per direction runs the whole tree of every image */
+    long long get_image(DTYPE* imgs) { return tree_get_image(imgs); } /* all B images; elements copied */
+    int fused() const { return tree_fused(); }                        /* 1: one launch per direction runs the whole tree of every image */
 
-    /* geometry (valid unless W_CREATION_ERROR): nodes of a depth per image = 4^depth; elements of one node of one image, 0 for a bad depth */
-    long long node_shape(int depth, int* nr, int* nc) const;
     static int geometry(int Nr, int Nc, int hlen, int levels, int* nr, int* nc); /* WaveletPackets::geometry */
     static int path_index(const char* path, int* depth);                         /* WaveletPackets::path_index */
 
-    /* copy out / in: elements copied, 0 when refused.  A node is the (B, nr, nc) stack of that node across the images (a pitched copy);
-     * get_level copies the whole depth (B, 4^depth, nr, nc).  set_node as WaveletPackets::set_node, with such a stack. */
-    long long get_node(DTYPE* out, int depth, int idx);
-    long long get_level(DTYPE* out, int depth);
-    long long set_node(DTYPE* in, int depth, int idx, int mem_is_on_device = 0);
-    intptr_t node_int_ptr(int depth, int idx, long long* pitch = NULL); /* image 0's node; *pitch = elements between images */
+    /* copy out / in: elements copied, 0 when refused.  A node is the (B, nr, nc) stack of that node across the images (a pitched copy).
+     * set_node as WaveletPackets::set_node, with such a stack. */
+    long long get_node(DTYPE* out, int depth, int idx) { return tree_get_node(out, depth, idx); }
+    long long set_node(DTYPE* in, int depth, int idx, int mem_is_on_device = 0) { return tree_set_node(in, depth, idx, mem_is_on_device); }
+    /* image 0's node; *pitch = elements between images */
+    intptr_t node_int_ptr(int depth, int idx, long long* pitch = NULL) { return tree_node_ptr(depth, idx, pitch); }
 
     /* additive costs of a depth (0 .. L): per_image (B * 4^depth entries, image-major) and / or summed over the images in image order
      * (4^depth entries); either may be NULL.  kind 0 "l1", 1 "shannon".  PDWT_OK or a negative code. */
     int node_costs(int depth, int kind, double* per_image, double* summed);
-    int best_basis(int kind); /* over the summed costs; a parent is kept when its cost is <= its children's.  Returns the basis size */
-    int set_basis(const int* depth, const int* idx, int n);
-    int basis_size() const;
-    int get_basis(int* depth, int* idx) const;
 
-    /* on the nodes of the current basis in every image; the all-"a" node only when do_thresh_appcoeffs */
-    void soft_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
-    void hard_threshold(DTYPE beta, int do_thresh_appcoeffs = 0);
-    double norm1();                    /* sum |c| over the basis and the images, in double; -1 when refused */
-    int images_norm1(double* out);     /* the same per image (B entries) */
-    int node_stats(int depth, w_band_stats* out); /* per (image, node): B * 4^depth entries, image-major (median_abs NaN) */
-    double estimate_sigma();           /* pooled: median |node "d"| over all images / 0.6744897501960817; -1 when refused */
-    int images_estimate_sigma(double* out); /* the same per image (B entries) */
-
-  private:
-    void* priv_;
-    void threshold(int op, DTYPE beta, int do_thresh_appcoeffs);
-    WaveletPacketsImages(const WaveletPacketsImages&);
-    WaveletPacketsImages& operator=(const WaveletPacketsImages&);
+    double norm1();                         /* sum |c| over the basis and the images, in double (the images_norm1 entries in image order); -1 when refused */
+    int images_norm1(double* out);          /* the same per image (B entries) */
+    int images_estimate_sigma(double* out); /* estimate_sigma per image (B entries), each from its own node "d" */
 };
 
 #endif

@@ -420,99 +420,50 @@ def host(dtype):
             getattr(L, pfx + "threshold_bands").argtypes = [vp, vp, ci]
             getattr(L, pfx + "denoise").restype = C.c_double
             getattr(L, pfx + "denoise").argtypes = [vp, ci, C.c_double, ci, vp]
-        # WaveletPackets (include/wpt.h, wpt.cpp)
+        # WaveletPackets, WaveletPackets1D, WaveletPacketsImages (include/wpt.h, wpt1d.h, wpt_batch.h; wpt.cpp): the handle functions the three
+        # share, then those whose arguments or return types are their class's
         pi = C.POINTER(ci)
-        L.pdwt_wpt_new.restype = vp
-        L.pdwt_wpt_new.argtypes = [vp, ci, ci, C.c_char_p, ci, ci]
-        for n in ("delete", "forward", "inverse", "state", "basis_size"):
-            getattr(L, "pdwt_wpt_" + n).argtypes = [vp]
-        L.pdwt_wpt_get_image.argtypes = [vp, vp]
-        L.pdwt_wpt_set_image.argtypes = [vp, vp, ci]
+        pd, pll = C.POINTER(C.c_double), C.POINTER(C.c_longlong)
+        for pfx in ("pdwt_wpt_", "pdwt_wp1h_", "pdwt_wpbh_"):
+            for n in ("delete", "forward", "inverse", "state", "basis_size"):
+                getattr(L, pfx + n).argtypes = [vp]
+            getattr(L, pfx + "set_image").argtypes = [vp, vp, ci]
+            getattr(L, pfx + "node_shape").restype = C.c_longlong
+            getattr(L, pfx + "node_shape").argtypes = [vp, ci, pi, pi]
+            getattr(L, pfx + "path_index").argtypes = [C.c_char_p, pi]
+            getattr(L, pfx + "get_image").argtypes = [vp, vp]
+            getattr(L, pfx + "get_node").argtypes = [vp, vp, ci, ci]
+            getattr(L, pfx + "get_level").restype = C.c_longlong
+            getattr(L, pfx + "get_level").argtypes = [vp, vp, ci]
+            getattr(L, pfx + "set_node").argtypes = [vp, vp, ci, ci, ci]
+            getattr(L, pfx + "node_int_ptr").restype = C.c_ssize_t
+            getattr(L, pfx + "best_basis").argtypes = [vp, ci]
+            getattr(L, pfx + "set_basis").argtypes = [vp, pi, pi, ci]
+            getattr(L, pfx + "get_basis").argtypes = [vp, pi, pi]
+            for n in ("soft_threshold", "hard_threshold"):
+                getattr(L, pfx + n).argtypes = [vp, ct, ci]
+            getattr(L, pfx + "norm1").restype = C.c_double
+            getattr(L, pfx + "norm1").argtypes = [vp]
+            getattr(L, pfx + "node_stats").argtypes = [vp, ci, C.POINTER(BandStats)]
+            getattr(L, pfx + "estimate_sigma").restype = C.c_double
+            getattr(L, pfx + "estimate_sigma").argtypes = [vp]
+        L.pdwt_wpt_new.restype = L.pdwt_wp1h_new.restype = L.pdwt_wpbh_new.restype = vp
+        L.pdwt_wpt_new.argtypes = L.pdwt_wp1h_new.argtypes = [vp, ci, ci, C.c_char_p, ci, ci]
+        L.pdwt_wpbh_new.argtypes = [vp, ci, ci, ci, C.c_char_p, ci, ci, ci]
         L.pdwt_wpt_info.argtypes = [vp, C.POINTER(InfoWPT)]
-        L.pdwt_wpt_node_shape.restype = C.c_longlong
-        L.pdwt_wpt_node_shape.argtypes = [vp, ci, pi, pi]
-        L.pdwt_wpt_path_index.argtypes = [C.c_char_p, pi]
-        L.pdwt_wpt_geometry.argtypes = [ci, ci, ci, ci, pi, pi]
-        L.pdwt_wpt_get_node.argtypes = [vp, vp, ci, ci]
-        L.pdwt_wpt_get_level.restype = C.c_longlong
-        L.pdwt_wpt_get_level.argtypes = [vp, vp, ci]
-        L.pdwt_wpt_set_node.argtypes = [vp, vp, ci, ci, ci]
-        L.pdwt_wpt_node_int_ptr.restype = C.c_ssize_t
-        L.pdwt_wpt_node_int_ptr.argtypes = [vp, ci, ci]
-        L.pdwt_wpt_node_costs.argtypes = [vp, ci, ci, C.POINTER(C.c_double)]
-        L.pdwt_wpt_best_basis.argtypes = [vp, ci]
-        L.pdwt_wpt_set_basis.argtypes = [vp, pi, pi, ci]
-        L.pdwt_wpt_get_basis.argtypes = [vp, pi, pi]
-        for n in ("soft_threshold", "hard_threshold"):
-            getattr(L, "pdwt_wpt_" + n).argtypes = [vp, ct, ci]
-        L.pdwt_wpt_norm1.restype = C.c_double
-        L.pdwt_wpt_norm1.argtypes = [vp]
-        L.pdwt_wpt_node_stats.argtypes = [vp, ci, C.POINTER(BandStats)]
-        L.pdwt_wpt_estimate_sigma.restype = C.c_double
-        L.pdwt_wpt_estimate_sigma.argtypes = [vp]
-        # WaveletPackets1D (include/wpt1d.h, wpt1d.cpp)
-        L.pdwt_wp1h_new.restype = vp
-        L.pdwt_wp1h_new.argtypes = [vp, ci, ci, C.c_char_p, ci, ci]
-        for n in ("delete", "forward", "inverse", "state", "basis_size", "fused"):
-            getattr(L, "pdwt_wp1h_" + n).argtypes = [vp]
-        L.pdwt_wp1h_get_image.argtypes = [vp, vp]
-        L.pdwt_wp1h_set_image.argtypes = [vp, vp, ci]
         L.pdwt_wp1h_info.argtypes = [vp, C.POINTER(InfoWPT1)]
-        L.pdwt_wp1h_node_shape.restype = C.c_longlong
-        L.pdwt_wp1h_node_shape.argtypes = [vp, ci, pi, pi]
-        L.pdwt_wp1h_path_index.argtypes = [C.c_char_p, pi]
+        L.pdwt_wpbh_info.argtypes = [vp, C.POINTER(InfoWPTB)]
+        L.pdwt_wpt_geometry.argtypes = L.pdwt_wpbh_geometry.argtypes = [ci, ci, ci, ci, pi, pi]
         L.pdwt_wp1h_geometry.argtypes = [ci, ci, ci, pi]
         L.pdwt_wp1h_frequency_order.argtypes = [ci, pi]
-        L.pdwt_wp1h_get_node.argtypes = [vp, vp, ci, ci]
-        L.pdwt_wp1h_get_level.restype = C.c_longlong
-        L.pdwt_wp1h_get_level.argtypes = [vp, vp, ci]
-        L.pdwt_wp1h_set_node.argtypes = [vp, vp, ci, ci, ci]
-        L.pdwt_wp1h_node_int_ptr.restype = C.c_ssize_t
-        L.pdwt_wp1h_node_int_ptr.argtypes = [vp, ci, ci, C.POINTER(C.c_longlong)]
-        L.pdwt_wp1h_node_costs.argtypes = [vp, ci, ci, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        L.pdwt_wp1h_best_basis.argtypes = [vp, ci]
-        L.pdwt_wp1h_set_basis.argtypes = [vp, pi, pi, ci]
-        L.pdwt_wp1h_get_basis.argtypes = [vp, pi, pi]
-        for n in ("soft_threshold", "hard_threshold"):
-            getattr(L, "pdwt_wp1h_" + n).argtypes = [vp, ct, ci]
-        L.pdwt_wp1h_norm1.restype = C.c_double
-        L.pdwt_wp1h_norm1.argtypes = [vp]
-        L.pdwt_wp1h_node_stats.argtypes = [vp, ci, C.POINTER(BandStats)]
-        L.pdwt_wp1h_estimate_sigma.restype = C.c_double
-        L.pdwt_wp1h_estimate_sigma.argtypes = [vp]
-        # WaveletPacketsImages (include/wpt_batch.h, wptb.cpp)
-        L.pdwt_wpbh_new.restype = vp
-        L.pdwt_wpbh_new.argtypes = [vp, ci, ci, ci, C.c_char_p, ci, ci, ci]
-        for n in ("delete", "forward", "inverse", "state", "basis_size", "fused"):
-            getattr(L, "pdwt_wpbh_" + n).argtypes = [vp]
-        L.pdwt_wpbh_get_image.restype = C.c_longlong
-        L.pdwt_wpbh_get_image.argtypes = [vp, vp]
-        L.pdwt_wpbh_set_image.argtypes = [vp, vp, ci]
-        L.pdwt_wpbh_info.argtypes = [vp, C.POINTER(InfoWPTB)]
-        L.pdwt_wpbh_node_shape.restype = C.c_longlong
-        L.pdwt_wpbh_node_shape.argtypes = [vp, ci, pi, pi]
-        L.pdwt_wpbh_path_index.argtypes = [C.c_char_p, pi]
-        L.pdwt_wpbh_geometry.argtypes = [ci, ci, ci, ci, pi, pi]
-        for n in ("get_node", "get_level", "set_node"):
+        L.pdwt_wp1h_fused.argtypes = L.pdwt_wpbh_fused.argtypes = [vp]
+        L.pdwt_wpt_node_int_ptr.argtypes = [vp, ci, ci]
+        L.pdwt_wp1h_node_int_ptr.argtypes = L.pdwt_wpbh_node_int_ptr.argtypes = [vp, ci, ci, pll]
+        L.pdwt_wpt_node_costs.argtypes = [vp, ci, ci, pd]
+        L.pdwt_wp1h_node_costs.argtypes = L.pdwt_wpbh_node_costs.argtypes = [vp, ci, ci, pd, pd]
+        for n in ("get_image", "get_node", "set_node"):  # the element counts of a stack
             getattr(L, "pdwt_wpbh_" + n).restype = C.c_longlong
-        L.pdwt_wpbh_get_node.argtypes = [vp, vp, ci, ci]
-        L.pdwt_wpbh_get_level.argtypes = [vp, vp, ci]
-        L.pdwt_wpbh_set_node.argtypes = [vp, vp, ci, ci, ci]
-        L.pdwt_wpbh_node_int_ptr.restype = C.c_ssize_t
-        L.pdwt_wpbh_node_int_ptr.argtypes = [vp, ci, ci, C.POINTER(C.c_longlong)]
-        L.pdwt_wpbh_node_costs.argtypes = [vp, ci, ci, C.POINTER(C.c_double), C.POINTER(C.c_double)]
-        L.pdwt_wpbh_best_basis.argtypes = [vp, ci]
-        L.pdwt_wpbh_set_basis.argtypes = [vp, pi, pi, ci]
-        L.pdwt_wpbh_get_basis.argtypes = [vp, pi, pi]
-        for n in ("soft_threshold", "hard_threshold"):
-            getattr(L, "pdwt_wpbh_" + n).argtypes = [vp, ct, ci]
-        L.pdwt_wpbh_norm1.restype = C.c_double
-        L.pdwt_wpbh_norm1.argtypes = [vp]
-        L.pdwt_wpbh_images_norm1.argtypes = [vp, C.POINTER(C.c_double)]
-        L.pdwt_wpbh_node_stats.argtypes = [vp, ci, C.POINTER(BandStats)]
-        L.pdwt_wpbh_estimate_sigma.restype = C.c_double
-        L.pdwt_wpbh_estimate_sigma.argtypes = [vp]
-        L.pdwt_wpbh_images_estimate_sigma.argtypes = [vp, C.POINTER(C.c_double)]
+        L.pdwt_wpbh_images_norm1.argtypes = L.pdwt_wpbh_images_estimate_sigma.argtypes = [vp, pd]
         # BoundaryWavelets (include/wt_ext.h, wt_ext.cpp)
         L.pdwt_bw_new.restype = vp
         L.pdwt_bw_new.argtypes = [vp, ci, ci, C.c_char_p, ci, ci, ci]

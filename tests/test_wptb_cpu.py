@@ -1,8 +1,9 @@
 """CPU-only: the batched 2-D wavelet packet layer loads and its device-free logic is right -- the exported symbols of the three libraries,
 the geometry against WaveletPackets::geometry, the plan of the fused form (pdwt_wptb_fused / pdwt_wptb_lds_bytes / pdwt_wptb_tmp_elems: the
 shapes DESIGN 3.17 tabulates, monotone in the image size, the largest fused square found by search through the plan function), the
-node-state table of the inverse and the chunk lists of its per-depth form, every refusal of the whole-transform drivers (refused before
-anything touches a device) and the transcript of failed constructions of WaveletPacketsImages."""
+node-state table of the inverse and the chunk lists of its per-depth form, and every refusal of the whole-transform drivers (refused before
+anything touches a device).  The transcript of failed constructions of WaveletPacketsImages is in test_packets_host_cpu.py, with those of
+the other two packet classes."""
 import ctypes as C
 
 import numpy as np
@@ -221,110 +222,7 @@ def test_drivers_refuse_bad_arguments(sfx, FT):
     assert inv(fake, tab, 4, 256, 256, 3, mixed, fake, None, C.byref(f), 1) == -1  # (beyond the budget: per depth whatever is allowed)
 
 
-# ---- the host class without a device -------------------------------------------------------------------------------------------------
-EXPECTED_METHODS = """state -> 4
-fused -> 0
-node_shape -> 0
-forward
-Warning: forward transform not computed, as there was an error when creating the wavelets
-inverse
-Warning: inverse transform not computed, as there was an error in a previous stage
-get_image -> 0
-set_image
-get_node -> 0
-get_level -> 0
-set_node -> 0
-Warning: set_node(): refused, the tree does not hold the coefficients of a forward() (run forward() first)
-node_int_ptr -> 0
-node_costs -> -1
-best_basis -> -1
-set_basis -> -1
-basis_size -> 0
-get_basis -> 0
-soft_threshold
-hard_threshold
-norm1 -> -1.0
-images_norm1 -> -1
-node_stats -> -1
-estimate_sigma -> -1.0
-images_estimate_sigma -> -1
-state -> 4
-delete
-"""
-VOID = ("delete", "forward", "inverse", "soft_threshold", "hard_threshold", "set_image")
-CASES = {
-    "no images": ((0, 64, 64, b"db4", 3), "ERROR: WaveletPacketsImages(): a batch holds 1 .. 65535 images (0 given)\n", "0 64 64 3 0"),
-    "too many images": ((65536, 64, 64, b"db4", 3), "ERROR: WaveletPacketsImages(): a batch holds 1 .. 65535 images (65536 given)\n", "65536 64 64 3 0"),
-    "bad size": ((4, 0, 64, b"db4", 3), "ERROR: WaveletPacketsImages(): invalid image size or wavelet name\n", "4 0 64 3 0"),
-    "2^31 elements": ((4, 65536, 32768, b"db4", 3), "ERROR: WaveletPacketsImages(): invalid image size or wavelet name\n", "4 65536 32768 3 0"),
-    "no name": ((4, 64, 64, None, 3), "ERROR: WaveletPacketsImages(): invalid image size or wavelet name\n", "4 64 64 3 0"),
-    "unknown wavelet": ((4, 64, 64, b"nosuchwavelet", 3), "ERROR: unknown wavelet name nosuchwavelet\n", "4 64 64 3 0"),
-    "too small": ((4, 6, 64, b"db4", 2),
-                  "Warning: required level (2) is greater than the maximum possible level for db4 packets (0) on a 6x64 image.\nForcing nlevels = 0\n"
-                  "ERROR: a 6x64 image is too small for one level of db4\n", "4 6 64 0 8"),
-    "too many nodes": ((65535, 64, 64, b"haar", 4), "ERROR: WaveletPacketsImages(): 65535 images of 256 nodes exceed 2^22 nodes per depth\n", "65535 64 64 4 2"),
-}
-
-
-def transcript(dtype, args, capfd):
-    L = nat.host(dtype)
-    libc = C.CDLL(None)
-    ct = C.c_float if np.dtype(dtype) == np.float32 else C.c_double
-    lines = []
-
-    def call(name, *a, show=None):
-        capfd.readouterr()
-        ret = getattr(L, "pdwt_wpbh_" + name)(*a)
-        libc.fflush(None)
-        lines.append(name if name in VOID else "%s -> %s" % (name, show(ret) if show else ret))
-        lines.extend(capfd.readouterr().out.splitlines())
-        return ret
-
-    h = call("new", None, *args, 1, 1, show=lambda r: "handle" if r else "NULL")
-    assert h
-    info = nat.InfoWPTB()
-    call("info", h, C.byref(info), show=lambda r: " ".join(str(getattr(info, f)) for f in ("B", "Nr", "Nc", "nlevels", "hlen")))
-    buf = np.zeros(64, dtype=dtype)
-    p = buf.ctypes.data_as(C.c_void_p)
-    dbl = (C.c_double * 8)()
-    ints = (C.c_int * 8)()
-    stats = (nat.BandStats * 8)()
-    call("state", h)
-    call("fused", h)
-    call("node_shape", h, 1, None, None)
-    call("forward", h)
-    call("inverse", h)
-    call("get_image", h, p)
-    call("set_image", h, p, 0)
-    call("get_node", h, p, 1, 0)
-    call("get_level", h, p, 1)
-    call("set_node", h, p, 1, 0, 0)
-    call("node_int_ptr", h, 1, 0, None)
-    call("node_costs", h, 1, 0, dbl, dbl)
-    call("best_basis", h, 0)
-    call("set_basis", h, ints, ints, 1)
-    call("basis_size", h)
-    call("get_basis", h, ints, ints)
-    call("soft_threshold", h, ct(1.0), 1)
-    call("hard_threshold", h, ct(1.0), 0)
-    call("norm1", h)
-    call("images_norm1", h, dbl)
-    call("node_stats", h, 1, stats)
-    call("estimate_sigma", h)
-    call("images_estimate_sigma", h, dbl)
-    call("state", h)
-    call("delete", h)
-    return "\n".join(lines) + "\n"
-
-
-@pytest.mark.parametrize("dtype", [np.float32, np.float64])
-@pytest.mark.parametrize("case", list(CASES))
-def test_failed_construction_transcript(case, dtype, capfd):
-    args, head, info = CASES[case]
-    got = transcript(dtype, args, capfd)
-    assert got == "new -> handle\n" + head + "info -> " + info + "\n" + EXPECTED_METHODS
-
-
+# ---- the host class without a device (its transcript of failed constructions: test_packets_host_cpu.py) -----------------------------
 def test_class_refuses_to_construct_without_a_gpu():
     if pdwt_amd.hip().pdwt_device_count() > 0:
         pytest.skip("a GPU is present")
