@@ -5,23 +5,23 @@
 //   forward   x-y: volume (z, y, x) -> 4 quadrants (z, hy, hx) in d_tmp    one plane tile per workgroup, rows and columns in LDS
 //             z:   4 quadrants      -> the 8 bands (hz, hy, hx)           lanes across a plane, 16 outputs per thread along z
 //   inverse   z first (bands -> quadrants), then x-y (quadrants -> volume).
+// The x-y kernels are the shared tile stages of tile_stages.hpp (with the packet and the boundary-mode tile kernels) on one plane; the
+// z kernels are written here.
 // Per output sample the tap order and the one-FMA-per-tap accumulation are the oracle's: the 3-D result is bit-identical to
 // composing the 1-D level along the axes (Haar excepted, within 1 ulp: the oracle's 1-D Haar level scales a +- b in double).
 // Traffic per level: one read of the input (plus the tile halos) and one write of the quadrants, then one read of the quadrants
 // and one write of the bands -- twice the compulsory bytes of a fully fused level.
-#include "vol3d.hpp"
+#include "tile_stages.hpp"
 
 namespace pdwt {
 
-// ---- forward x-y level: one plane tile per workgroup ----------------------------------------------------
-// A workgroup owns FTY x FTX output positions (half resolution) of one plane z.  It stages the input rows / columns the tile
-// needs (with the periodic halo, wrap_ext per sample index) in LDS, runs the row pass into an LDS buffer (lo | hi per row)
-// and the column pass out of it, and writes the four quadrants (x band, y band) of the tile: one read of the plane (plus halo)
-// and one write of its four quadrants.  Per output the taps run j = 0 .. HL-1, one FMA each -- the oracle's row, then column.
-constexpr int kXYThreads = 256;
-constexpr int FTX = 32, FTY = 16;  // forward tile (output positions)
-constexpr int ITX = 64, ITY = 32;  // inverse tile (output samples, even starts)
-
+// ---- x-y level: one plane tile per workgroup ------------------------------------------------------------
+// Forward: a workgroup owns TFY x TFX output positions (half resolution) of one plane z.  It stages the input rows / columns the tile
+// needs (with the periodic halo, wrap_ext per sample index) in LDS, runs the row pass into an LDS buffer (lo | hi per row) and the
+// column pass out of it, and writes the four quadrants (x band, y band) of the tile: one read of the plane (plus halo) and one write
+// of its four quadrants.  Inverse: TIY x TIX output samples of one plane; the windows of the four quadrants staged with wrap_per, the
+// synthesis along y into an LDS buffer (x low | x high), then along x into the output.  The stages and their summation order (the
+// oracle's row, then column; its syn_lines rule): tile_stages.hpp.
 template <typename T>
 struct XYJob {
     const T* src;     // forward: the level's input volume (z, ny, nx); inverse: unused
@@ -31,132 +31,42 @@ struct XYJob {
 };
 
 template <typename T, int HL>
-constexpr size_t fwd_xy_lds()
-{
-    return sizeof(T) * ((size_t)(2 * FTY + HL - 2) * (2 * FTX + HL - 2) + 2 * (size_t)(2 * FTY + HL - 2) * FTX);
-}
-template <typename T, int HL>
-constexpr size_t inv_xy_lds()
-{
-    return sizeof(T) * (4 * (size_t)(ITY / 2 + HL / 2) * (ITX / 2 + HL / 2) + 2 * (size_t)ITY * (ITX / 2 + HL / 2));
-}
-
-template <typename T, int HL>
-__global__ __launch_bounds__(kXYThreads) void k_fwd_xy(XYJob<T> job, Taps2<T> taps)
+__global__ __launch_bounds__(kTileThreads) void k_fwd_xy(XYJob<T> job, Taps2<T> taps)
 {
     extern __shared__ double smem_d[];  // (double: 8-byte alignment for either precision)
-    constexpr int RI = 2 * FTY + HL - 2, CI = 2 * FTX + HL - 2, c = HL / 2 - 1;
+    constexpr int RI = tile_fwd_win(TFY, HL), CI = tile_fwd_win(TFX, HL), c = HL / 2 - 1;
     T* in = reinterpret_cast<T*>(smem_d);  // [RI][CI]
-    T* rb = in + RI * CI;                  // [2][RI][FTX]: row pass lo | hi
+    T* rb = in + RI * CI;                  // [2][RI][TFX]: row pass lo | hi
     const int tid = threadIdx.x, z = blockIdx.z;
-    const int ox0 = blockIdx.x * FTX, oy0 = blockIdx.y * FTY;
-    const int nx = job.nx, ny = job.ny;
-    const T* __restrict__ plane = job.src + (size_t)z * ny * nx;
-    const int gx0 = 2 * ox0 - c, gy0 = 2 * oy0 - c;
-    for (int e = tid; e < RI * CI; e += kXYThreads) {
-        const int r = e / CI, cc = e - r * CI;  // (compile-time divisor)
-        in[e] = plane[(size_t)wrap_ext(gy0 + r, ny) * nx + wrap_ext(gx0 + cc, nx)];
-    }
-    __syncthreads();
-    for (int e = tid; e < RI * FTX; e += kXYThreads) {
-        const int r = e / FTX, ox = e % FTX;
-        const T* p = in + r * CI + 2 * ox;
-        const int z0 = opaque_zero();
-        T sl = T(0), sh = T(0);
-#pragma unroll
-        for (int j = 0; j < HL; j++) {
-            const T v = p[j];
-            sl = fma_t<T>(v, taps.a[HL - 1 - j + z0], sl);
-            sh = fma_t<T>(v, taps.b[HL - 1 - j + z0], sh);
-        }
-        rb[e] = sl;
-        rb[RI * FTX + e] = sh;
-    }
-    __syncthreads();
+    const int ox0 = blockIdx.x * TFX, oy0 = blockIdx.y * TFY;
     const size_t zoff = (size_t)z * job.hy * job.hx;
-    for (int e = tid; e < FTY * FTX; e += kXYThreads) {
-        const int oy = e / FTX, ox = e % FTX;
-        if (oy0 + oy >= job.hy || ox0 + ox >= job.hx) continue;
-        const size_t o = zoff + (size_t)(oy0 + oy) * job.hx + (ox0 + ox);
-#pragma unroll
-        for (int xb = 0; xb < 2; xb++) {
-            const T* p = rb + xb * RI * FTX + (2 * oy) * FTX + ox;
-            const int z0 = opaque_zero();
-            T sl = T(0), sh = T(0);
-#pragma unroll
-            for (int j = 0; j < HL; j++) {
-                const T v = p[j * FTX];
-                sl = fma_t<T>(v, taps.a[HL - 1 - j + z0], sl);
-                sh = fma_t<T>(v, taps.b[HL - 1 - j + z0], sh);
-            }
-            job.q[2 * xb][o] = sl;
-            job.q[2 * xb + 1][o] = sh;
-        }
-    }
+    tile_stage_window_per<T, RI, CI, kTileThreads>(in, job.src + (size_t)z * job.ny * job.nx, job.ny, job.nx, 2 * oy0 - c, 2 * ox0 - c, tid);
+    tile_rows_analysis<T, HL, RI, CI, TFX, kTileThreads>(in, rb, taps, tid);
+    tile_cols_analysis_write<T, HL, RI, TFX, TFY, kTileThreads>(rb, taps, job.q[0] + zoff, job.q[1] + zoff, job.q[2] + zoff, job.q[3] + zoff, job.hy, job.hx,
+                                                                oy0, ox0, tid);
 }
 
-// ---- inverse x-y level: ITY x ITX output samples of one plane per workgroup ------------------------------
-// Stages the window of the four quadrants the tile needs (wrap_per), runs the synthesis along y into an LDS buffer (x low |
-// x high), then along x into the output.  Synthesis rule of the oracle's syn_lines, the two branch sums added once.
 template <typename T, int HL>
-__global__ __launch_bounds__(kXYThreads) void k_inv_xy(XYJob<T> job, Taps2<T> taps)
+__global__ __launch_bounds__(kTileThreads) void k_inv_xy(XYJob<T> job, Taps2<T> taps)
 {
     extern __shared__ double smem_d[];
-    constexpr int h2 = HL / 2, c = h2 / 2, shift = (h2 & 1) ? 0 : 1;
-    constexpr int WR = ITY / 2 + h2, WC = ITX / 2 + h2;
+    constexpr int c = HL / 4, SH = syn_shift(HL);
+    constexpr int WR = tile_inv_win(TIY, HL, true), WC = tile_inv_win(TIX, HL, true);
     T* in = reinterpret_cast<T*>(smem_d);  // [4][WR][WC]
-    T* cb = in + 4 * WR * WC;              // [2][ITY][WC]: y synthesis of the x-low / x-high pairs
+    T* cb = in + 4 * WR * WC;              // [2][TIY][WC]: y synthesis of the x-low / x-high pairs
     const int tid = threadIdx.x, z = blockIdx.z;
-    const int g0x = blockIdx.x * ITX, g0y = blockIdx.y * ITY;  // even
-    const int hx = job.hx, hy = job.hy;
-    const int wx0 = g0x / 2 - c, wy0 = g0y / 2 - c;
-    const size_t zoff = (size_t)z * hy * hx;
-    for (int e = tid; e < 4 * WR * WC; e += kXYThreads) {
-        const int qd = e / (WR * WC), rem = e - qd * (WR * WC), r = rem / WC, cc = rem - r * WC;
-        in[e] = job.q[qd][zoff + (size_t)wrap_per(wy0 + r, hy) * hx + wrap_per(wx0 + cc, hx)];
-    }
-    __syncthreads();
-    for (int e = tid; e < 2 * ITY * WC; e += kXYThreads) {
-        const int xb = e / (ITY * WC), rem = e - xb * (ITY * WC), gy = rem / WC, cc = rem - gy * WC;
-        const int gp = gy + shift, lp = gp >> 1;
-        const bool odd_tap = (gp & 1) == 0;
-        const T* pa = in + (2 * xb) * WR * WC + lp * WC + cc;
-        const T* pd = pa + WR * WC;
-        T sa = T(0), sd = T(0);
-#pragma unroll
-        for (int j = 0; j < h2; j++) {
-            const T fl = odd_tap ? taps.a[HL - 2 - 2 * j] : taps.a[HL - 1 - 2 * j];
-            const T fh = odd_tap ? taps.b[HL - 2 - 2 * j] : taps.b[HL - 1 - 2 * j];
-            sa = fma_t<T>(pa[j * WC], fl, sa);
-            sd = fma_t<T>(pd[j * WC], fh, sd);
-        }
-        cb[e] = sa + sd;
-    }
-    __syncthreads();
-    const int nx = job.nx, ny = job.ny;
-    T* __restrict__ plane = job.dst + (size_t)z * ny * nx;
-    for (int e = tid; e < ITY * ITX; e += kXYThreads) {
-        const int gy = e / ITX, gx = e % ITX;
-        if (g0y + gy >= ny || g0x + gx >= nx) continue;
-        const int gp = gx + shift, lp = gp >> 1;
-        const bool odd_tap = (gp & 1) == 0;
-        const T* pa = cb + gy * WC + lp;
-        const T* pd = pa + ITY * WC;
-        T sa = T(0), sd = T(0);
-#pragma unroll
-        for (int j = 0; j < h2; j++) {
-            const T fl = odd_tap ? taps.a[HL - 2 - 2 * j] : taps.a[HL - 1 - 2 * j];
-            const T fh = odd_tap ? taps.b[HL - 2 - 2 * j] : taps.b[HL - 1 - 2 * j];
-            sa = fma_t<T>(pa[j], fl, sa);
-            sd = fma_t<T>(pd[j], fh, sd);
-        }
-        plane[(size_t)(g0y + gy) * nx + (g0x + gx)] = sa + sd;
-    }
+    const int g0x = blockIdx.x * TIX, g0y = blockIdx.y * TIY;  // even
+    const size_t zoff = (size_t)z * job.hy * job.hx;
+    tile_stage_children_per<T, WR, WC, kTileThreads>(in, [&](int qd) { return job.q[qd] + zoff; }, job.hy, job.hx, g0y / 2 - c, g0x / 2 - c, tid);
+    tile_cols_synthesis<T, HL, SH, WR, WC, TIY, kTileThreads>(in, cb, taps, tid);
+    tile_rows_synthesis_write<T, HL, SH, WC, TIY, TIX, kTileThreads>(cb, taps, job.dst + (size_t)z * job.ny * job.nx, job.ny, job.nx, g0y, g0x, tid);
 }
 
 // ---- z pass: ZC outputs per thread along z from a register window -----------------------------------------
 // Lanes run across a plane (coalesced), blockIdx.y = chunk of ZC outputs along z, blockIdx.z = quadrant.  The thread loads the
-// 2*ZC + HL - 2 input planes of its chunk ONCE into registers and computes every output of the chunk from them.
+// 2*ZC + HL - 2 input planes of its chunk ONCE into registers and computes every output of the chunk from them.  These loops read the
+// taps straight from the kernel argument and are therefore written here, not in tile_stages.hpp: a function that takes the taps
+// by reference makes the compiler load all 2 * HL of them at the kernel's entry, which does not fit the SGPRs of a long float64 bank.
 constexpr int kZThreads = 256;
 constexpr int ZC = 16;
 
@@ -205,7 +115,7 @@ __global__ __launch_bounds__(kZThreads) void k_syn_z(ZJob<T> job, Taps2<T> taps)
     const int k = blockIdx.x * kZThreads + threadIdx.x;
     if (k >= job.plane) return;
     const int e = blockIdx.z, g0 = blockIdx.y * ZC;  // even
-    constexpr int h2 = HL / 2, c = h2 / 2, shift = (h2 & 1) ? 0 : 1, W = ZC / 2 + h2;
+    constexpr int h2 = HL / 2, c = h2 / 2, shift = syn_shift(HL), W = ZC / 2 + h2;
     const int nin = job.nin, q0 = g0 / 2 - c;
     const size_t pl = (size_t)job.plane;
     const T* __restrict__ a = job.src[e] + k;
@@ -240,13 +150,13 @@ static int launch_level(int dir, int pass, const XYJob<T>& xy, const ZJob<T>& zj
 {
     if (pass == 0) {  // x-y
         const bool fwd = dir == 0;
-        const size_t lds = fwd ? fwd_xy_lds<T, HL>() : inv_xy_lds<T, HL>();
+        const size_t lds = fwd ? tile_fwd_lds<T, HL>(false) : tile_inv_lds<T, HL>(true);
         const void* kfn = fwd ? (const void*)k_fwd_xy<T, HL> : (const void*)k_inv_xy<T, HL>;
         if (lds > 64 * 1024)
             if (const int rc = lds_opt_in_ptr(kfn); rc != PDWT_OK) return rc;
-        const dim3 grid = fwd ? dim3(idiv_up(xy.hx, FTX), idiv_up(xy.hy, FTY), nz) : dim3(idiv_up(xy.nx, ITX), idiv_up(xy.ny, ITY), nz);
-        if (fwd) hipLaunchKernelGGL((k_fwd_xy<T, HL>), grid, dim3(kXYThreads), lds, stream(), xy, taps);
-        else hipLaunchKernelGGL((k_inv_xy<T, HL>), grid, dim3(kXYThreads), lds, stream(), xy, taps);
+        const dim3 grid = fwd ? dim3(idiv_up(xy.hx, TFX), idiv_up(xy.hy, TFY), nz) : dim3(idiv_up(xy.nx, TIX), idiv_up(xy.ny, TIY), nz);
+        if (fwd) hipLaunchKernelGGL((k_fwd_xy<T, HL>), grid, dim3(kTileThreads), lds, stream(), xy, taps);
+        else hipLaunchKernelGGL((k_inv_xy<T, HL>), grid, dim3(kTileThreads), lds, stream(), xy, taps);
     } else {  // z
         const dim3 grid(idiv_up(zj.plane, kZThreads), idiv_up(zj.nout, ZC), 4);
         if (dir == 0) hipLaunchKernelGGL((k_ana_z<T, HL>), grid, dim3(kZThreads), 0, stream(), zj, taps);

@@ -2,7 +2,8 @@
 // modes"; the class: include/wt_ext.h).  Unlike every other transform of the library this one does not periodise: the image is
 // extended past its borders by the mode (zero, constant, symmetric, reflect, periodic: PyWavelets' names and semantics) and the
 // bands have the expanded size (n + hlen - 1) / 2 per axis.  The inverse needs no extension at all.
-// Two tile kernels in the shape of the packet kernels (wpt2d.hip), their stages the device functions of dwt_ext.hpp:
+// Two tile kernels in the shape of the packet kernels (wpt2d.hip): the staging is that of dwt_ext.hpp, the passes are the stages of
+// tile_stages.hpp, which the packet and volume kernels run too:
 //   k_ext_fwd  16 x 32 positions of the four bands per workgroup: stage the input window in LDS (interior tiles with plain addressing,
 //              border tiles through the index map of the mode), row pass into LDS, column pass out of it, four band stores
 //   k_ext_inv  32 x 64 samples of the parent per workgroup: stage the four child windows (0 past the bands), column synthesis into
@@ -13,9 +14,9 @@
 
 namespace pdwt {
 
-constexpr int kExtThreads = 256;
-constexpr int EFX = 32, EFY = 16;  // forward tile (band positions)
-constexpr int EIX = 64, EIY = 32;  // inverse tile (parent samples, even starts)
+// The tile of tile_stages.hpp.  (tests/test_newer_bank_matrix_cpu.py reads these four from this file; the kernels use the shared constants.)
+constexpr int EFX = 32, EFY = 16, EIX = 64, EIY = 32;
+static_assert(EFX == TFX && EFY == TFY && EIX == TIX && EIY == TIY, "the tile shape is defined in tile_stages.hpp");
 
 template <typename T>
 struct ExtFwdJob {
@@ -31,66 +32,53 @@ struct ExtInvJob {
 };
 
 template <typename T, int HL>
-constexpr size_t ext_fwd_lds()
-{
-    constexpr size_t RI = 2 * EFY + HL - 2, CI = 2 * EFX + HL - 2;
-    return sizeof(T) * (RI * CI + 2 * RI * EFX) + sizeof(int) * (RI + CI);
-}
-template <typename T, int HL>
-constexpr size_t ext_inv_lds()
-{
-    constexpr size_t WR = EIY / 2 + HL / 2 - 1, WC = EIX / 2 + HL / 2 - 1;
-    return sizeof(T) * (4 * WR * WC + 2 * (size_t)EIY * WC);
-}
-
-template <typename T, int HL>
-__global__ __launch_bounds__(kExtThreads) void k_ext_fwd(ExtFwdJob<T> job, Taps2<T> taps)
+__global__ __launch_bounds__(kTileThreads) void k_ext_fwd(ExtFwdJob<T> job, Taps2<T> taps)
 {
     extern __shared__ double smem_d[];  // (double: 8-byte alignment for either precision)
-    constexpr int RI = 2 * EFY + HL - 2, CI = 2 * EFX + HL - 2;
-    T* in = reinterpret_cast<T*>(smem_d);              // [RI][CI]
-    T* rb = in + RI * CI;                              // [2][RI][EFX]: row pass lo | hi
-    int* map = reinterpret_cast<int*>(rb + 2 * RI * EFX);  // [RI + CI]: border tiles only
+    constexpr int RI = tile_fwd_win(TFY, HL), CI = tile_fwd_win(TFX, HL);
+    T* in = reinterpret_cast<T*>(smem_d);                  // [RI][CI]
+    T* rb = in + RI * CI;                                  // [2][RI][TFX]: row pass lo | hi
+    int* map = reinterpret_cast<int*>(rb + 2 * RI * TFX);  // [RI + CI]: border tiles only
     const int tid = threadIdx.x;
-    const int ox0 = blockIdx.x * EFX, oy0 = blockIdx.y * EFY;
+    const int ox0 = blockIdx.x * TFX, oy0 = blockIdx.y * TFY;
     // position i reads xe[2i + 1 - k], k = 0 .. HL-1: the window of the tile starts at 2 * o0 + 1 - (HL - 1)
-    ext_stage_window<T, RI, CI, kExtThreads>(in, map, job.src, job.nr, job.nc, 2 * oy0 + 2 - HL, 2 * ox0 + 2 - HL, job.mode, tid);
-    ext_rows_analysis<T, HL, RI, CI, EFX, kExtThreads>(in, rb, taps, tid);
-    ext_cols_analysis_write<T, HL, RI, EFX, EFY, kExtThreads>(rb, taps, job.a, job.h, job.v, job.d, job.hr, job.hc, oy0, ox0, tid);
+    ext_stage_window<T, RI, CI, kTileThreads>(in, map, job.src, job.nr, job.nc, 2 * oy0 + 2 - HL, 2 * ox0 + 2 - HL, job.mode, tid);
+    tile_rows_analysis<T, HL, RI, CI, TFX, kTileThreads>(in, rb, taps, tid);
+    tile_cols_analysis_write<T, HL, RI, TFX, TFY, kTileThreads>(rb, taps, job.a, job.h, job.v, job.d, job.hr, job.hc, oy0, ox0, tid);
 }
 
 template <typename T, int HL>
-__global__ __launch_bounds__(kExtThreads) void k_ext_inv(ExtInvJob<T> job, Taps2<T> taps)
+__global__ __launch_bounds__(kTileThreads) void k_ext_inv(ExtInvJob<T> job, Taps2<T> taps)
 {
     extern __shared__ double smem_d[];
-    constexpr int WR = EIY / 2 + HL / 2 - 1, WC = EIX / 2 + HL / 2 - 1;
+    constexpr int WR = tile_inv_win(TIY, HL, false), WC = tile_inv_win(TIX, HL, false);
     T* in = reinterpret_cast<T*>(smem_d);  // [4][WR][WC]
-    T* cb = in + 4 * WR * WC;              // [2][EIY][WC]
+    T* cb = in + 4 * WR * WC;              // [2][TIY][WC]
     const int tid = threadIdx.x;
-    const int g0x = blockIdx.x * EIX, g0y = blockIdx.y * EIY;  // even
-    ext_stage_children<T, WR, WC, kExtThreads>(in, job.q, job.hr, job.hc, g0y / 2, g0x / 2, tid);
-    ext_cols_synthesis<T, HL, WR, WC, EIY, kExtThreads>(in, cb, taps, tid);
-    ext_rows_synthesis_write<T, HL, WC, EIY, EIX, kExtThreads>(cb, taps, job.dst, job.nr, job.nc, g0y, g0x, tid);
+    const int g0x = blockIdx.x * TIX, g0y = blockIdx.y * TIY;  // even
+    ext_stage_children<T, WR, WC, kTileThreads>(in, job.q, job.hr, job.hc, g0y / 2, g0x / 2, tid);
+    tile_cols_synthesis<T, HL, 0, WR, WC, TIY, kTileThreads>(in, cb, taps, tid);
+    tile_rows_synthesis_write<T, HL, 0, WC, TIY, TIX, kTileThreads>(cb, taps, job.dst, job.nr, job.nc, g0y, g0x, tid);
 }
 
 // ---- drivers -----------------------------------------------------------------------------------------------------------------
 template <typename T, int HL>
 static int launch_ext_fwd(const ExtFwdJob<T>& job, const Taps2<T>& taps)
 {
-    constexpr size_t lds = ext_fwd_lds<T, HL>();
+    constexpr size_t lds = tile_fwd_lds<T, HL>(true);
     if (lds > 64 * 1024)
         if (const int rc = lds_opt_in_ptr((const void*)k_ext_fwd<T, HL>); rc != PDWT_OK) return rc;
-    hipLaunchKernelGGL((k_ext_fwd<T, HL>), dim3(idiv_up(job.hc, EFX), idiv_up(job.hr, EFY)), dim3(kExtThreads), lds, stream(), job, taps);
+    hipLaunchKernelGGL((k_ext_fwd<T, HL>), dim3(idiv_up(job.hc, TFX), idiv_up(job.hr, TFY)), dim3(kTileThreads), lds, stream(), job, taps);
     PDWT_HIP_TRY(hipGetLastError());
     return PDWT_OK;
 }
 template <typename T, int HL>
 static int launch_ext_inv(const ExtInvJob<T>& job, const Taps2<T>& taps)
 {
-    constexpr size_t lds = ext_inv_lds<T, HL>();
+    constexpr size_t lds = tile_inv_lds<T, HL>(false);
     if (lds > 64 * 1024)
         if (const int rc = lds_opt_in_ptr((const void*)k_ext_inv<T, HL>); rc != PDWT_OK) return rc;
-    hipLaunchKernelGGL((k_ext_inv<T, HL>), dim3(idiv_up(job.nc, EIX), idiv_up(job.nr, EIY)), dim3(kExtThreads), lds, stream(), job, taps);
+    hipLaunchKernelGGL((k_ext_inv<T, HL>), dim3(idiv_up(job.nc, TIX), idiv_up(job.nr, TIY)), dim3(kTileThreads), lds, stream(), job, taps);
     PDWT_HIP_TRY(hipGetLastError());
     return PDWT_OK;
 }
@@ -103,7 +91,7 @@ static bool ext_level_ok(int nr, int nc, int hlen)
     if (nr < 1 || nc < 1 || nr < hlen - 1 || nc < hlen - 1 || nr > (1 << 30) || nc > (1 << 30)) return false;
     if ((unsigned long long)nr * (unsigned long long)nc >= (1ull << 31)) return false;
     // rows of tiles are a grid dimension, in either direction
-    return idiv_up(ext_half(nr, hlen), EFY) <= 65535 && idiv_up(nr, EIY) <= 65535;
+    return idiv_up(ext_half(nr, hlen), TFY) <= 65535 && idiv_up(nr, TIY) <= 65535;
 }
 
 template <typename T>

@@ -62,7 +62,7 @@ static bool ext2db_level_ok(long long B, int nr, int nc, int hlen)
     if (B < 1 || B > kExt2dbMaxBatch) return false;
     if (nr < 1 || nc < 1 || nr < hlen - 1 || nc < hlen - 1 || nr > (1 << 30) || nc > (1 << 30)) return false;
     if ((unsigned long long)nr * (unsigned long long)nc >= (1ull << 31)) return false;
-    return idiv_up(ext_half(nr, hlen), X3FY) <= 65535 && idiv_up(nr, X3IY) <= 65535;
+    return idiv_up(ext_half(nr, hlen), TFY) <= 65535 && idiv_up(nr, TIY) <= 65535;
 }
 static bool ext2db_ok(long long B, int Nr, int Nc, int hlen, int levels)
 {

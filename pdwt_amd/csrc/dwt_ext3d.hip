@@ -2,7 +2,7 @@
 // boundary modes"; the class: BoundaryWavelets3D, include/wt_ext.h).  The one-axis formula of dwt_ext.hpp along x, then y, then z: a
 // level takes an nz x nr x nc approximation to eight bands of ((nz + F - 1) / 2) x ((nr + F - 1) / 2) x ((nc + F - 1) / 2); the inverse
 // runs z, y, x and needs no extension and no mode.  Two launches per level and direction, in the shape of dwt3d.hip:
-//   forward   x-y: volume (nz, nr, nc) -> 4 quadrants (nz, hr, hc) in d_tmp    the tile stages of dwt_ext.hpp, blockIdx.z = the plane
+//   forward   x-y: volume (nz, nr, nc) -> 4 quadrants (nz, hr, hc) in d_tmp    the tile stages of tile_stages.hpp, blockIdx.z = the plane
 //             z:   4 quadrants         -> the 8 bands (hz, hr, hc)            lanes across an expanded plane, 16 outputs per thread along z
 //   inverse   z first (bands -> quadrants), then x-y (quadrants -> volume).
 // A forward launch reads the extension only through ext_index.  Per output the tap order and the one-FMA-per-tap accumulation are
@@ -14,7 +14,7 @@
 
 namespace pdwt {
 
-// (the x-y tile sizes and Ext3XYJob: dwt_ext3d_xy.hpp)
+// (Ext3XYJob: dwt_ext3d_xy.hpp)
 constexpr int kX3ZThreads = 256;
 constexpr int X3ZC = 16;             // outputs per thread along z
 
@@ -27,56 +27,44 @@ struct Ext3ZJob {
     int nin, nout, plane, mode;
 };
 
+// ---- x-y passes: the staging of dwt_ext.hpp and the stages of tile_stages.hpp on plane blockIdx.z ------------------------------------
 template <typename T, int HL>
-constexpr size_t ext3_fwd_lds()
-{
-    constexpr size_t RI = 2 * X3FY + HL - 2, CI = 2 * X3FX + HL - 2;
-    return sizeof(T) * (RI * CI + 2 * RI * X3FX) + sizeof(int) * (RI + CI);
-}
-template <typename T, int HL>
-constexpr size_t ext3_inv_lds()
-{
-    constexpr size_t WR = X3IY / 2 + HL / 2 - 1, WC = X3IX / 2 + HL / 2 - 1;
-    return sizeof(T) * (4 * WR * WC + 2 * (size_t)X3IY * WC);
-}
-
-// ---- x-y passes: the stages of dwt_ext.hpp on plane blockIdx.z ---------------------------------------------------------------------
-template <typename T, int HL>
-__global__ __launch_bounds__(kX3Threads) void k_ext3_fwd_xy(Ext3XYJob<T> job, Taps2<T> taps)
+__global__ __launch_bounds__(kTileThreads) void k_ext3_fwd_xy(Ext3XYJob<T> job, Taps2<T> taps)
 {
     extern __shared__ double smem_d[];  // (double: 8-byte alignment for either precision)
-    constexpr int RI = 2 * X3FY + HL - 2, CI = 2 * X3FX + HL - 2;
-    T* in = reinterpret_cast<T*>(smem_d);                   // [RI][CI]
-    T* rb = in + RI * CI;                                   // [2][RI][X3FX]: row pass lo | hi
-    int* map = reinterpret_cast<int*>(rb + 2 * RI * X3FX);  // [RI + CI]: border tiles only
+    constexpr int RI = tile_fwd_win(TFY, HL), CI = tile_fwd_win(TFX, HL);
+    T* in = reinterpret_cast<T*>(smem_d);                  // [RI][CI]
+    T* rb = in + RI * CI;                                  // [2][RI][TFX]: row pass lo | hi
+    int* map = reinterpret_cast<int*>(rb + 2 * RI * TFX);  // [RI + CI]: border tiles only
     const int tid = threadIdx.x;
-    const int ox0 = blockIdx.x * X3FX, oy0 = blockIdx.y * X3FY;
+    const int ox0 = blockIdx.x * TFX, oy0 = blockIdx.y * TFY;
     const T* plane = job.src + (size_t)blockIdx.z * job.nr * job.nc;
     const size_t zoff = (size_t)blockIdx.z * job.hr * job.hc;
-    ext_stage_window<T, RI, CI, kX3Threads>(in, map, plane, job.nr, job.nc, 2 * oy0 + 2 - HL, 2 * ox0 + 2 - HL, job.mode, tid);
-    ext_rows_analysis<T, HL, RI, CI, X3FX, kX3Threads>(in, rb, taps, tid);
-    ext_cols_analysis_write<T, HL, RI, X3FX, X3FY, kX3Threads>(rb, taps, job.q[0] + zoff, job.q[1] + zoff, job.q[2] + zoff, job.q[3] + zoff, job.hr,
-                                                               job.hc, oy0, ox0, tid);
+    ext_stage_window<T, RI, CI, kTileThreads>(in, map, plane, job.nr, job.nc, 2 * oy0 + 2 - HL, 2 * ox0 + 2 - HL, job.mode, tid);
+    tile_rows_analysis<T, HL, RI, CI, TFX, kTileThreads>(in, rb, taps, tid);
+    tile_cols_analysis_write<T, HL, RI, TFX, TFY, kTileThreads>(rb, taps, job.q[0] + zoff, job.q[1] + zoff, job.q[2] + zoff, job.q[3] + zoff, job.hr, job.hc,
+                                                                oy0, ox0, tid);
 }
 
 template <typename T, int HL>
-__global__ __launch_bounds__(kX3Threads) void k_ext3_inv_xy(Ext3XYJob<T> job, Taps2<T> taps)
+__global__ __launch_bounds__(kTileThreads) void k_ext3_inv_xy(Ext3XYJob<T> job, Taps2<T> taps)
 {
     extern __shared__ double smem_d[];
-    constexpr int WR = X3IY / 2 + HL / 2 - 1, WC = X3IX / 2 + HL / 2 - 1;
+    constexpr int WR = tile_inv_win(TIY, HL, false), WC = tile_inv_win(TIX, HL, false);
     T* in = reinterpret_cast<T*>(smem_d);  // [4][WR][WC]
-    T* cb = in + 4 * WR * WC;              // [2][X3IY][WC]
+    T* cb = in + 4 * WR * WC;              // [2][TIY][WC]
     const int tid = threadIdx.x;
-    const int g0x = blockIdx.x * X3IX, g0y = blockIdx.y * X3IY;  // even
+    const int g0x = blockIdx.x * TIX, g0y = blockIdx.y * TIY;  // even
     const size_t zoff = (size_t)blockIdx.z * job.hr * job.hc;
     const T* const q[4] = {job.q[0] + zoff, job.q[1] + zoff, job.q[2] + zoff, job.q[3] + zoff};
-    ext_stage_children<T, WR, WC, kX3Threads>(in, q, job.hr, job.hc, g0y / 2, g0x / 2, tid);
-    ext_cols_synthesis<T, HL, WR, WC, X3IY, kX3Threads>(in, cb, taps, tid);
-    ext_rows_synthesis_write<T, HL, WC, X3IY, X3IX, kX3Threads>(cb, taps, job.dst + (size_t)blockIdx.z * job.nr * job.nc, job.nr, job.nc, g0y, g0x, tid);
+    ext_stage_children<T, WR, WC, kTileThreads>(in, q, job.hr, job.hc, g0y / 2, g0x / 2, tid);
+    tile_cols_synthesis<T, HL, 0, WR, WC, TIY, kTileThreads>(in, cb, taps, tid);
+    tile_rows_synthesis_write<T, HL, 0, WC, TIY, TIX, kTileThreads>(cb, taps, job.dst + (size_t)blockIdx.z * job.nr * job.nc, job.nr, job.nc, g0y, g0x, tid);
 }
 
 // ---- z passes: X3ZC outputs per thread along z from a register window --------------------------------------------------------------
-// Lanes run across an expanded plane (coalesced), blockIdx.y = chunk of X3ZC outputs along z, blockIdx.z = quadrant.
+// Lanes run across an expanded plane (coalesced), blockIdx.y = chunk of X3ZC outputs along z, blockIdx.z = quadrant.  (Written here
+// like the z kernels of dwt3d.hip, and for the reason given there.)
 // Analysis: output i reads xe[2i + 1 - k], k = 0 .. HL-1, so the window of the chunk from i0 holds the 2 * X3ZC + HL - 2 planes from
 // the extended index 2 * i0 + 2 - HL; each plane index goes through ext_index (-1: the plane is 0).  A chunk whose window lies inside
 // the volume skips the map (a workgroup-uniform branch).
@@ -160,12 +148,12 @@ __global__ __launch_bounds__(kX3ZThreads) void k_ext3_syn_z(Ext3ZJob<T> job, Tap
 template <typename T, int HL>
 static int launch_ext3_xy(bool fwd, const Ext3XYJob<T>& xy, int nz, const Taps2<T>& taps)
 {
-    const size_t lds = fwd ? ext3_fwd_lds<T, HL>() : ext3_inv_lds<T, HL>();
+    const size_t lds = fwd ? tile_fwd_lds<T, HL>(true) : tile_inv_lds<T, HL>(false);
     const void* kfn = fwd ? (const void*)k_ext3_fwd_xy<T, HL> : (const void*)k_ext3_inv_xy<T, HL>;
     if (lds > 64 * 1024)
         if (const int rc = lds_opt_in_ptr(kfn); rc != PDWT_OK) return rc;
-    if (fwd) hipLaunchKernelGGL((k_ext3_fwd_xy<T, HL>), dim3(idiv_up(xy.hc, X3FX), idiv_up(xy.hr, X3FY), nz), dim3(kX3Threads), lds, stream(), xy, taps);
-    else hipLaunchKernelGGL((k_ext3_inv_xy<T, HL>), dim3(idiv_up(xy.nc, X3IX), idiv_up(xy.nr, X3IY), nz), dim3(kX3Threads), lds, stream(), xy, taps);
+    if (fwd) hipLaunchKernelGGL((k_ext3_fwd_xy<T, HL>), dim3(idiv_up(xy.hc, TFX), idiv_up(xy.hr, TFY), nz), dim3(kTileThreads), lds, stream(), xy, taps);
+    else hipLaunchKernelGGL((k_ext3_inv_xy<T, HL>), dim3(idiv_up(xy.nc, TIX), idiv_up(xy.nr, TIY), nz), dim3(kTileThreads), lds, stream(), xy, taps);
     PDWT_HIP_TRY(hipGetLastError());
     return PDWT_OK;
 }

@@ -1,15 +1,12 @@
-// dwt_ext3d_xy.hpp -- the x-y pass of dwt_ext3d.hip as other translation units see it: the tile sizes, the job and the launch.  The
-// kernels (k_ext3_fwd_xy / k_ext3_inv_xy: the tile stages of dwt_ext.hpp on plane blockIdx.z) are instantiated in dwt_ext3d.hip alone;
+// dwt_ext3d_xy.hpp -- the x-y pass of dwt_ext3d.hip as other translation units see it: the job and the launch (the tile: tile_stages.hpp).
+// The kernels (k_ext3_fwd_xy / k_ext3_inv_xy: the staging of dwt_ext.hpp and the stages of tile_stages.hpp on plane blockIdx.z) are
+// instantiated in dwt_ext3d.hip alone;
 // the batched 2-D transform (dwt_ext2db.hip) runs them with the planes = the images of a batch and the four quadrant pointers aimed at
 // its band stacks.
 #pragma once
 #include "dwt_ext.hpp"
 
 namespace pdwt {
-
-constexpr int kX3Threads = 256;
-constexpr int X3FX = 32, X3FY = 16;  // forward x-y tile (band positions): the tile of dwt_ext.hip
-constexpr int X3IX = 64, X3IY = 32;  // inverse x-y tile (parent samples, even starts)
 
 template <typename T>
 struct Ext3XYJob {
@@ -32,7 +29,7 @@ inline bool ext3_level_ok(int nz, int nr, int nc, int hlen)
     if (nz < 1 || nr < 1 || nc < 1 || nz < hlen - 1 || nr < hlen - 1 || nc < hlen - 1) return false;
     if (nz > 65535 || nr > (1 << 30) || nc > (1 << 30)) return false;
     if ((unsigned long long)nr * (unsigned long long)nc >= (1ull << 31)) return false;  // (the expanded plane is no larger: n >= hlen - 1)
-    return idiv_up(ext_half(nr, hlen), X3FY) <= 65535 && idiv_up(nr, X3IY) <= 65535;
+    return idiv_up(ext_half(nr, hlen), TFY) <= 65535 && idiv_up(nr, TIY) <= 65535;
 }
 
 // band k (aaa, aad, ada, add, daa, dad, dda, ddd: bits z y x) of quadrant q (2 * x band + y band) and z band zb

@@ -26,7 +26,7 @@
 namespace pdwt {
 
 constexpr size_t kAdjLdsMax = 160 * 1024;
-constexpr int kAdjThreads = 256;
+constexpr int kAdjThreads = 256;  // the fold kernel (the synthesis kernel: kTileThreads)
 constexpr int AFY = 32, AFX = 8;  // fold tile (samples)
 constexpr int kAdjMaxBatch = 65535;
 constexpr int kAdjMaxLev = 32;
@@ -42,29 +42,23 @@ struct AdjJob {
 };
 
 template <typename T, int HL>
-constexpr size_t adj_syn_lds()
-{
-    constexpr size_t WR = X3IY / 2 + HL / 2 - 1, WC = X3IX / 2 + HL / 2 - 1;
-    return sizeof(T) * (4 * WR * WC + 2 * (size_t)X3IY * WC);
-}
-
-template <typename T, int HL>
-__global__ __launch_bounds__(kAdjThreads) void k_ext_adj_syn(AdjJob<T> job, Taps2<T> taps)
+__global__ __launch_bounds__(kTileThreads) void k_ext_adj_syn(AdjJob<T> job, Taps2<T> taps)
 {
     extern __shared__ double smem_d[];
-    constexpr int WR = X3IY / 2 + HL / 2 - 1, WC = X3IX / 2 + HL / 2 - 1;
+    constexpr int WR = tile_inv_win(TIY, HL, false), WC = tile_inv_win(TIX, HL, false);
     T* in = reinterpret_cast<T*>(smem_d);  // [4][WR][WC]
-    T* cb = in + 4 * WR * WC;              // [2][X3IY][WC]
+    T* cb = in + 4 * WR * WC;              // [2][TIY][WC]
     const int tid = threadIdx.x;
-    const int g0x = blockIdx.x * X3IX, g0y = blockIdx.y * X3IY;  // even cells of the extended grid
+    const int g0x = blockIdx.x * TIX, g0y = blockIdx.y * TIY;  // even cells of the extended grid
     const int Er = adj_ext_len(job.nr, HL), Ec = adj_ext_len(job.nc, HL);
     const size_t zoff = (size_t)blockIdx.z * job.hr * job.hc;
     const T* const q[4] = {job.q[0] + zoff, job.q[1] + zoff, job.q[2] + zoff, job.q[3] + zoff};
-    adj_stage_children<T, WR, WC, kAdjThreads>(in, q, job.hr, job.hc, g0y / 2 - (HL / 2 - 1), g0x / 2 - (HL / 2 - 1), tid);
-    ext_cols_synthesis<T, HL, WR, WC, X3IY, kAdjThreads>(in, cb, taps, tid);
+    // the windows of the PADDED bands: the origin in band coordinates may be negative
+    ext_stage_children<T, WR, WC, kTileThreads>(in, q, job.hr, job.hc, g0y / 2 - (HL / 2 - 1), g0x / 2 - (HL / 2 - 1), tid);
+    tile_cols_synthesis<T, HL, 0, WR, WC, TIY, kTileThreads>(in, cb, taps, tid);
     T* frame = job.frame ? job.frame + (size_t)blockIdx.z * adj_frame_elems(job.nr, job.nc, HL) : nullptr;
-    adj_rows_synthesis_write<T, HL, WC, X3IY, X3IX, kAdjThreads>(cb, taps, job.dst + (size_t)blockIdx.z * job.nr * job.nc, frame, job.nr, job.nc, Er, Ec, g0y,
-                                                                 g0x, tid);
+    adj_rows_synthesis_write<T, HL, WC, TIY, TIX, kTileThreads>(cb, taps, job.dst + (size_t)blockIdx.z * job.nr * job.nc, frame, job.nr, job.nc, Er, Ec, g0y,
+                                                                g0x, tid);
 }
 
 // the longest run of samples [y0, y1) x [x0, x1) of either axis that no halo cell repeats (host; from ext_index): a tile inside both runs
@@ -197,8 +191,8 @@ bool adj2_level_ok(long long B, int nr, int nc, int hlen)
     if (nr < 1 || nc < 1 || nr < hlen - 1 || nc < hlen - 1 || nr > (1 << 30) || nc > (1 << 30)) return false;
     if ((unsigned long long)nr * (unsigned long long)nc >= (1ull << 31)) return false;
     // what the forward and inverse tile kernels take, and the rows of tiles of the extended grid
-    if (idiv_up(ext_half(nr, hlen), X3FY) > 65535 || idiv_up(nr, X3IY) > 65535) return false;
-    return idiv_up(adj_ext_len(nr, hlen), X3IY) <= 65535;
+    if (idiv_up(ext_half(nr, hlen), TFY) > 65535 || idiv_up(nr, TIY) > 65535) return false;
+    return idiv_up(adj_ext_len(nr, hlen), TIY) <= 65535;
 }
 static bool adj2_ok(long long B, int Nr, int Nc, int hlen, int levels)
 {
@@ -243,11 +237,11 @@ static Adj1Plan adj1_plan(int nc, int hlen, int levels, size_t elem)
 template <typename T, int HL>
 static int launch_adj_syn(const AdjJob<T>& job, int B, const Taps2<T>& taps)
 {
-    constexpr size_t lds = adj_syn_lds<T, HL>();
+    constexpr size_t lds = tile_inv_lds<T, HL>(false);
     if (lds > 64 * 1024)
         if (const int rc = lds_opt_in_ptr((const void*)k_ext_adj_syn<T, HL>); rc != PDWT_OK) return rc;
-    const dim3 grid(idiv_up(adj_ext_len(job.nc, HL), X3IX), idiv_up(adj_ext_len(job.nr, HL), X3IY), B);
-    hipLaunchKernelGGL((k_ext_adj_syn<T, HL>), grid, dim3(kAdjThreads), lds, stream(), job, taps);
+    const dim3 grid(idiv_up(adj_ext_len(job.nc, HL), TIX), idiv_up(adj_ext_len(job.nr, HL), TIY), B);
+    hipLaunchKernelGGL((k_ext_adj_syn<T, HL>), grid, dim3(kTileThreads), lds, stream(), job, taps);
     PDWT_HIP_TRY(hipGetLastError());
     return PDWT_OK;
 }

@@ -8,7 +8,8 @@
 // u is a synthesis onto the EXTENDED line.  With the reversed taps L'[j] = L[F-1-j] and the cell e = s + F - 2 of the extended line
 //   u[e] = sum_i' a'[i'] L'[e + F - 2 - 2i'],   a'[i'] = abar[i' - (F/2 - 1)]  (0 outside 0 .. N-1)
 // which is the inverse formula of dwt_ext.hpp on a coefficient line padded with F/2 - 1 zeros on either side: the pair functions of the
-// inverse (ext1d_inv_item, ext_cols_synthesis) are reused as they are, on E = 2N + F - 2 = 2 (N + F/2 - 1) cells.
+// inverse (ext1d_inv_item; tile_cols_synthesis of tile_stages.hpp with SHIFT 0) are reused as they are, on E = 2N + F - 2 =
+// 2 (N + F/2 - 1) cells.
 // The fold is a gather in a fixed order (no floating-point atomics): the pre-images come from ext_index itself, never from a count.
 //
 // The 1-D stages take the thread count as a template argument and the thread index as an argument and contain no barrier, like those
@@ -154,30 +155,12 @@ __host__ __device__ inline size_t adj_frame_index(int ey, int ex, int nr, int nc
     return (size_t)(Er - nr) * Ec + (size_t)(ey - (F - 2)) * (Ec - nc) + (ex < F - 2 ? ex : ex - nc);
 }
 
-// ext_stage_children with an origin that may be negative: the windows of the four PADDED bands (origin in padded coordinates, i.e.
-// band row wy0 - (F/2 - 1)); 0 outside a band on every side.  Ends with a barrier.
-template <typename T, int WR, int WC, int NT>
-__device__ __forceinline__ void adj_stage_children(T* in, const T* const* q, int hr, int hc, int wy0, int wx0, int tid)
-{
-#pragma unroll
-    for (int qd = 0; qd < 4; qd++) {
-        const T* __restrict__ band = q[qd];
-        for (int e = tid; e < WR * WC; e += NT) {
-            const int r = e / WC, cc = e - r * WC;
-            const int y = wy0 + r, x = wx0 + cc;
-            in[qd * WR * WC + e] = ((unsigned)y < (unsigned)hr && (unsigned)x < (unsigned)hc) ? band[(size_t)y * hc + x] : T(0);
-        }
-    }
-    __syncthreads();
-}
-
-// ext_rows_synthesis_write onto the extended grid: the GY x GX cells from (g0y, g0x) of the Er x Ec grid; a cell of the sample range is
-// stored to the image, any other to the frame (NULL: dropped, mode zero).
+// tile_rows_synthesis_write (SHIFT 0) onto the extended grid: the GY x GX cells from (g0y, g0x) of the Er x Ec grid; a cell of the
+// sample range is stored to the image, any other to the frame (NULL: dropped, mode zero).
 template <typename T, int HL, int WC, int GY, int GX, int NT>
 __device__ __forceinline__ void adj_rows_synthesis_write(const T* cb, const Taps2<T>& taps, T* __restrict__ dst, T* __restrict__ frame, int nr, int nc, int Er,
                                                          int Ec, int g0y, int g0x, int tid)
 {
-    constexpr int h2 = HL / 2;
     for (int e = tid; e < GY * GX; e += NT) {
         const int gy = e / GX, gx = e % GX;
         const int ey = g0y + gy, ex = g0x + gx;
@@ -185,19 +168,10 @@ __device__ __forceinline__ void adj_rows_synthesis_write(const T* cb, const Taps
         const int sy = ey - (HL - 2), sx = ex - (HL - 2);
         const bool real = (unsigned)sy < (unsigned)nr && (unsigned)sx < (unsigned)nc;
         if (!real && !frame) continue;
-        const bool odd = gx & 1;
         const T* pa = cb + gy * WC + (gx >> 1);
-        const T* pd = pa + GY * WC;
-        T sa = T(0), sd = T(0);
-#pragma unroll
-        for (int m = 0; m < h2; m++) {
-            const T fl = odd ? taps.a[HL - 1 - 2 * m] : taps.a[HL - 2 - 2 * m];
-            const T fh = odd ? taps.b[HL - 1 - 2 * m] : taps.b[HL - 2 - 2 * m];
-            sa = fma_t<T>(pa[m], fl, sa);
-            sd = fma_t<T>(pd[m], fh, sd);
-        }
-        if (real) dst[(size_t)sy * nc + sx] = sa + sd;
-        else frame[adj_frame_index(ey, ex, nr, nc, Er, Ec, HL)] = sa + sd;
+        const T u = syn_dot<T, HL, 1>(pa, pa + GY * WC, gx, taps);
+        if (real) dst[(size_t)sy * nc + sx] = u;
+        else frame[adj_frame_index(ey, ex, nr, nc, Er, Ec, HL)] = u;
     }
 }
 

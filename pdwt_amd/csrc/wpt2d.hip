@@ -4,18 +4,20 @@
 // children 4i + {0: A, 1: H, 2: V, 3: D} in the array of depth l + 1.  One depth step is therefore a batched one-level 2-D
 // transform of small images, and runs in ONE launch: one workgroup per (tile, node), blockIdx.z = the position in the (optional)
 // list of parent nodes.  The tile kernels are the x-y kernels of dwt3d.hip with a node in the place of a plane and the quadrants
-// written straight to the children: stage the tile with its periodic halo in LDS, row pass into LDS, column pass out of it.
+// written straight to the children: stage the tile with its periodic halo in LDS, row pass into LDS, column pass out of it -- the
+// stages of tile_stages.hpp, which both files call; the kernels here only place the node and its children.
 // Per output the taps run in the order of the checker's separable level, one FMA per tap (rows, then columns), so one level of
 // a node has the arithmetic of the one-level 2-D transform of that node.  Haar (hlen 2) runs the clamped 2x2 butterfly of the
 // reference's Haar level (src/haar.cu:10-58) instead.
 // Traffic per depth and direction: one read of the parents (plus the tile halos) and one write of the children.
-#include "vol3d.hpp"
+#include "tile_stages.hpp"
 
 namespace pdwt {
 
-constexpr int kWpThreads = 256;
-constexpr int WFX = 32, WFY = 16;  // forward tile (child positions)
-constexpr int WIX = 64, WIY = 32;  // inverse tile (parent samples, even starts)
+constexpr int kWpThreads = 256;    // the Haar and cost kernels (the tile kernels: kTileThreads)
+// The tile of tile_stages.hpp.  (tests/test_newer_bank_matrix_cpu.py reads these four from this file; the kernels use the shared constants.)
+constexpr int WFX = 32, WFY = 16, WIX = 64, WIY = 32;
+static_assert(WFX == TFX && WFY == TFY && WIX == TIX && WIY == TIY, "the tile shape is defined in tile_stages.hpp");
 constexpr int kWpMaxNodes = 16384; // 4^7: the node count is a grid dimension
 
 template <typename T>
@@ -26,133 +28,43 @@ struct WpJob {
     int nr, nc, hr, hc;
 };
 
+// ---- forward: TFY x TFX positions of the four children of one parent node per workgroup ----------------------------------
 template <typename T, int HL>
-constexpr size_t wp_fwd_lds()
-{
-    return sizeof(T) * ((size_t)(2 * WFY + HL - 2) * (2 * WFX + HL - 2) + 2 * (size_t)(2 * WFY + HL - 2) * WFX);
-}
-template <typename T, int HL>
-constexpr size_t wp_inv_lds()
-{
-    return sizeof(T) * (4 * (size_t)(WIY / 2 + HL / 2) * (WIX / 2 + HL / 2) + 2 * (size_t)WIY * (WIX / 2 + HL / 2));
-}
-
-// ---- forward: WFY x WFX positions of the four children of one parent node per workgroup ----------------------------------
-template <typename T, int HL>
-__global__ __launch_bounds__(kWpThreads) void k_wp_fwd(WpJob<T> job, Taps2<T> taps)
+__global__ __launch_bounds__(kTileThreads) void k_wp_fwd(WpJob<T> job, Taps2<T> taps)
 {
     extern __shared__ double smem_d[];  // (double: 8-byte alignment for either precision)
-    constexpr int RI = 2 * WFY + HL - 2, CI = 2 * WFX + HL - 2, c = HL / 2 - 1;
+    constexpr int RI = tile_fwd_win(TFY, HL), CI = tile_fwd_win(TFX, HL), c = HL / 2 - 1;
     T* in = reinterpret_cast<T*>(smem_d);  // [RI][CI]
-    T* rb = in + RI * CI;                  // [2][RI][WFX]: row pass lo | hi
+    T* rb = in + RI * CI;                  // [2][RI][TFX]: row pass lo | hi
     const int tid = threadIdx.x;
     const int node = job.nodes ? job.nodes[blockIdx.z] : (int)blockIdx.z;
-    const int ox0 = blockIdx.x * WFX, oy0 = blockIdx.y * WFY;
-    const int nc = job.nc, nr = job.nr;
-    const T* __restrict__ parent = job.src + (size_t)node * nr * nc;
-    const int gx0 = 2 * ox0 - c, gy0 = 2 * oy0 - c;
-    for (int e = tid; e < RI * CI; e += kWpThreads) {
-        const int r = e / CI, cc = e - r * CI;  // (compile-time divisor)
-        in[e] = parent[(size_t)wrap_ext(gy0 + r, nr) * nc + wrap_ext(gx0 + cc, nc)];
-    }
-    __syncthreads();
-    for (int e = tid; e < RI * WFX; e += kWpThreads) {
-        const int r = e / WFX, ox = e % WFX;
-        const T* p = in + r * CI + 2 * ox;
-        const int z0 = opaque_zero();
-        T sl = T(0), sh = T(0);
-#pragma unroll
-        for (int j = 0; j < HL; j++) {
-            const T v = p[j];
-            sl = fma_t<T>(v, taps.a[HL - 1 - j + z0], sl);
-            sh = fma_t<T>(v, taps.b[HL - 1 - j + z0], sh);
-        }
-        rb[e] = sl;
-        rb[RI * WFX + e] = sh;
-    }
-    __syncthreads();
+    const int ox0 = blockIdx.x * TFX, oy0 = blockIdx.y * TFY;
     const size_t cs = (size_t)job.hr * job.hc;  // child stride
-    T* __restrict__ child = job.dst + 4 * (size_t)node * cs;
-    for (int e = tid; e < WFY * WFX; e += kWpThreads) {
-        const int oy = e / WFX, ox = e % WFX;
-        if (oy0 + oy >= job.hr || ox0 + ox >= job.hc) continue;
-        const size_t o = (size_t)(oy0 + oy) * job.hc + (ox0 + ox);
-#pragma unroll
-        for (int xb = 0; xb < 2; xb++) {  // row low: A (column low), H (column high); row high: V, D
-            const T* p = rb + xb * RI * WFX + (2 * oy) * WFX + ox;
-            const int z0 = opaque_zero();
-            T sl = T(0), sh = T(0);
-#pragma unroll
-            for (int j = 0; j < HL; j++) {
-                const T v = p[j * WFX];
-                sl = fma_t<T>(v, taps.a[HL - 1 - j + z0], sl);
-                sh = fma_t<T>(v, taps.b[HL - 1 - j + z0], sh);
-            }
-            child[(2 * xb) * cs + o] = sl;
-            child[(2 * xb + 1) * cs + o] = sh;
-        }
-    }
+    T* child = job.dst + 4 * (size_t)node * cs;  // A, H, V, D = children 4 node + 0 .. 3
+    tile_stage_window_per<T, RI, CI, kTileThreads>(in, job.src + (size_t)node * job.nr * job.nc, job.nr, job.nc, 2 * oy0 - c, 2 * ox0 - c, tid);
+    tile_rows_analysis<T, HL, RI, CI, TFX, kTileThreads>(in, rb, taps, tid);
+    tile_cols_analysis_write<T, HL, RI, TFX, TFY, kTileThreads>(rb, taps, child, child + cs, child + 2 * cs, child + 3 * cs, job.hr, job.hc, oy0, ox0, tid);
 }
 
-// ---- inverse: WIY x WIX samples of one parent node per workgroup ----------------------------------------------------------
-// Stages the window of the four children the tile needs (wrap_per), runs the synthesis along the columns into an LDS buffer
-// ((A, H) | (V, D)), then along the rows into the parent.  The oracle's syn_lines rule, the two branch sums added once.
+// ---- inverse: TIY x TIX samples of one parent node per workgroup ----------------------------------------------------------
+// The four child windows staged with wrap_per, synthesis along the columns into LDS ((A, H) | (V, D)), then along the rows into the
+// parent: the oracle's syn_lines rule (the stages of tile_stages.hpp with the shift of the periodised synthesis).
 template <typename T, int HL>
-__global__ __launch_bounds__(kWpThreads) void k_wp_inv(WpJob<T> job, Taps2<T> taps)
+__global__ __launch_bounds__(kTileThreads) void k_wp_inv(WpJob<T> job, Taps2<T> taps)
 {
     extern __shared__ double smem_d[];
-    constexpr int h2 = HL / 2, c = h2 / 2, shift = (h2 & 1) ? 0 : 1;
-    constexpr int WR = WIY / 2 + h2, WC = WIX / 2 + h2;
+    constexpr int c = HL / 4, SH = syn_shift(HL);
+    constexpr int WR = tile_inv_win(TIY, HL, true), WC = tile_inv_win(TIX, HL, true);
     T* in = reinterpret_cast<T*>(smem_d);  // [4][WR][WC]
-    T* cb = in + 4 * WR * WC;              // [2][WIY][WC]
+    T* cb = in + 4 * WR * WC;              // [2][TIY][WC]
     const int tid = threadIdx.x;
     const int node = job.nodes ? job.nodes[blockIdx.z] : (int)blockIdx.z;
-    const int g0x = blockIdx.x * WIX, g0y = blockIdx.y * WIY;  // even
-    const int hc = job.hc, hr = job.hr;
-    const int wx0 = g0x / 2 - c, wy0 = g0y / 2 - c;
-    const size_t cs = (size_t)hr * hc;
-    const T* __restrict__ child = job.src + 4 * (size_t)node * cs;
-    for (int e = tid; e < 4 * WR * WC; e += kWpThreads) {
-        const int qd = e / (WR * WC), rem = e - qd * (WR * WC), r = rem / WC, cc = rem - r * WC;
-        in[e] = child[qd * cs + (size_t)wrap_per(wy0 + r, hr) * hc + wrap_per(wx0 + cc, hc)];
-    }
-    __syncthreads();
-    for (int e = tid; e < 2 * WIY * WC; e += kWpThreads) {
-        const int xb = e / (WIY * WC), rem = e - xb * (WIY * WC), gy = rem / WC, cc = rem - gy * WC;
-        const int gp = gy + shift, lp = gp >> 1;
-        const bool odd_tap = (gp & 1) == 0;
-        const T* pa = in + (2 * xb) * WR * WC + lp * WC + cc;
-        const T* pd = pa + WR * WC;
-        T sa = T(0), sd = T(0);
-#pragma unroll
-        for (int j = 0; j < h2; j++) {
-            const T fl = odd_tap ? taps.a[HL - 2 - 2 * j] : taps.a[HL - 1 - 2 * j];
-            const T fh = odd_tap ? taps.b[HL - 2 - 2 * j] : taps.b[HL - 1 - 2 * j];
-            sa = fma_t<T>(pa[j * WC], fl, sa);
-            sd = fma_t<T>(pd[j * WC], fh, sd);
-        }
-        cb[e] = sa + sd;
-    }
-    __syncthreads();
-    const int nc = job.nc, nr = job.nr;
-    T* __restrict__ parent = job.dst + (size_t)node * nr * nc;
-    for (int e = tid; e < WIY * WIX; e += kWpThreads) {
-        const int gy = e / WIX, gx = e % WIX;
-        if (g0y + gy >= nr || g0x + gx >= nc) continue;
-        const int gp = gx + shift, lp = gp >> 1;
-        const bool odd_tap = (gp & 1) == 0;
-        const T* pa = cb + gy * WC + lp;
-        const T* pd = pa + WIY * WC;
-        T sa = T(0), sd = T(0);
-#pragma unroll
-        for (int j = 0; j < h2; j++) {
-            const T fl = odd_tap ? taps.a[HL - 2 - 2 * j] : taps.a[HL - 1 - 2 * j];
-            const T fh = odd_tap ? taps.b[HL - 2 - 2 * j] : taps.b[HL - 1 - 2 * j];
-            sa = fma_t<T>(pa[j], fl, sa);
-            sd = fma_t<T>(pd[j], fh, sd);
-        }
-        parent[(size_t)(g0y + gy) * nc + (g0x + gx)] = sa + sd;
-    }
+    const int g0x = blockIdx.x * TIX, g0y = blockIdx.y * TIY;  // even
+    const size_t cs = (size_t)job.hr * job.hc;
+    const T* child = job.src + 4 * (size_t)node * cs;
+    tile_stage_children_per<T, WR, WC, kTileThreads>(in, [=](int qd) { return child + qd * cs; }, job.hr, job.hc, g0y / 2 - c, g0x / 2 - c, tid);
+    tile_cols_synthesis<T, HL, SH, WR, WC, TIY, kTileThreads>(in, cb, taps, tid);
+    tile_rows_synthesis_write<T, HL, SH, WC, TIY, TIX, kTileThreads>(cb, taps, job.dst + (size_t)node * job.nr * job.nc, job.nr, job.nc, g0y, g0x, tid);
 }
 
 // ---- Haar: the clamped 2x2 butterfly, one thread per child position / parent sample ----------------------------------------
@@ -228,12 +140,12 @@ template <typename T, int HL>
 static int launch_wp(int dir, const WpJob<T>& job, int nnodes, const Taps2<T>& taps)
 {
     const bool fwd = dir == 0;
-    const size_t lds = fwd ? wp_fwd_lds<T, HL>() : wp_inv_lds<T, HL>();
+    const size_t lds = fwd ? tile_fwd_lds<T, HL>(false) : tile_inv_lds<T, HL>(true);
     const void* kfn = fwd ? (const void*)k_wp_fwd<T, HL> : (const void*)k_wp_inv<T, HL>;
     if (lds > 64 * 1024)
         if (const int rc = lds_opt_in_ptr(kfn); rc != PDWT_OK) return rc;
-    if (fwd) hipLaunchKernelGGL((k_wp_fwd<T, HL>), dim3(idiv_up(job.hc, WFX), idiv_up(job.hr, WFY), nnodes), dim3(kWpThreads), lds, stream(), job, taps);
-    else hipLaunchKernelGGL((k_wp_inv<T, HL>), dim3(idiv_up(job.nc, WIX), idiv_up(job.nr, WIY), nnodes), dim3(kWpThreads), lds, stream(), job, taps);
+    if (fwd) hipLaunchKernelGGL((k_wp_fwd<T, HL>), dim3(idiv_up(job.hc, TFX), idiv_up(job.hr, TFY), nnodes), dim3(kTileThreads), lds, stream(), job, taps);
+    else hipLaunchKernelGGL((k_wp_inv<T, HL>), dim3(idiv_up(job.nc, TIX), idiv_up(job.nr, TIY), nnodes), dim3(kTileThreads), lds, stream(), job, taps);
     PDWT_HIP_TRY(hipGetLastError());
     return PDWT_OK;
 }
@@ -251,7 +163,7 @@ static int wp_level(int dir, const T* src, T* dst, int nr, int nc, const int* d_
     job.src = src, job.dst = dst, job.nodes = d_nodes;
     job.nr = nr, job.nc = nc, job.hr = div2(nr), job.hc = div2(nc);
     // rows of tiles are a grid dimension too: refused here, before anything is launched
-    const int tile_rows = hlen == 2 ? (dir == 0 ? idiv_up(job.hr, 4) : idiv_up(nr, 4)) : (dir == 0 ? idiv_up(job.hr, WFY) : idiv_up(nr, WIY));
+    const int tile_rows = hlen == 2 ? (dir == 0 ? idiv_up(job.hr, 4) : idiv_up(nr, 4)) : (dir == 0 ? idiv_up(job.hr, TFY) : idiv_up(nr, TIY));
     if (tile_rows > 65535) return PDWT_EINVAL;
     if (hlen == 2) {
         const dim3 grid = dir == 0 ? dim3(idiv_up(job.hc, 64), tile_rows, nnodes) : dim3(idiv_up(nc, 64), tile_rows, nnodes);
