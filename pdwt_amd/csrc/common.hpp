@@ -73,6 +73,10 @@ struct KTimer {
         else hipLaunchKernelGGL(kernel, grid, block, lds, pdwt::stream(), __VA_ARGS__);                                    \
     } while (0)
 
+// ---- LDS: the ceiling, the opt-in, the launch, the barrier ------------------------------------------------------------------------
+constexpr size_t kLdsMax = 160 * 1024;   // the hard ceiling of a workgroup: what a host-side plan may ask for
+constexpr size_t kLdsOptIn = 64 * 1024;  // above it a kernel has to be opted in before it is launched
+
 // More than 64 KB of dynamic LDS per workgroup is opt-in per (kernel, device).  The driver call is made ONCE for each pair
 // (one function-local static per kernel: the kernel is the template argument) and asks for the most a kernel can ever request
 // (160 KB), so afterwards nothing but the launch itself is on the enqueue path.
@@ -84,7 +88,7 @@ inline int lds_opt_in()
     PDWT_HIP_TRY(hipGetDevice(&dev));
     const unsigned long long bit = 1ull << (dev & 63);
     if (!(done.load(std::memory_order_relaxed) & bit)) {
-        PDWT_HIP_TRY(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+        PDWT_HIP_TRY(hipFuncSetAttribute((const void*)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)kLdsMax));
         done.fetch_or(bit, std::memory_order_relaxed);
     }
     return PDWT_OK;
@@ -93,6 +97,26 @@ inline int lds_opt_in()
 // The same for kernels that are only known as a pointer at the call site (templates instantiated over many lengths): one driver
 // call per (kernel, device), remembered in a small table (runtime.hip); every later launch is a lookup.
 int lds_opt_in_ptr(const void* kernel);
+
+// One launch on the library stream with `lds` bytes of dynamic LDS: opt in above 64 KiB, launch, ask for the launch error.
+// PDWT_OK, or the error.  (Launches that carry the events of a KTimer go through PDWT_LAUNCH_KT instead.)
+template <typename... P, typename... A>
+inline int launch_lds(void (*kernel)(P...), dim3 grid, dim3 threads, size_t lds, const A&... args)
+{
+    if (lds > kLdsOptIn)
+        if (const int rc = lds_opt_in_ptr((const void*)kernel); rc != PDWT_OK) return rc;
+    hipLaunchKernelGGL(kernel, grid, threads, lds, stream(), args...);
+    PDWT_HIP_TRY(hipGetLastError());
+    return PDWT_OK;
+}
+
+// Workgroup barrier that orders LDS traffic only: __syncthreads() also drains vmcnt, so every barrier between two LDS stages would wait
+// for the global stores of the stage before it.  A hand-off through LDS only needs this wave's DS operations retired.
+__device__ __forceinline__ void lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+// the same as the `bar` / `sync` argument of the pipelines that run on a CPU too (dwt_ext2db.hpp, wpt2db.hpp, wpt1d.hpp)
+struct LdsBarrier {
+    __device__ __forceinline__ void operator()() const { lds_barrier(); }
+};
 
 // ---- in-kernel clock probe (pdwt_clock_probe_*, runtime.hip) ----------------------------------------------------
 // Workgroup 0 of a probed launch stores (s_memtime, s_memrealtime) when it starts and when it ends: the shader-clock count over

@@ -143,27 +143,17 @@ __global__ __launch_bounds__(kZThreads) void k_syn_z(ZJob<T> job, Taps2<T> taps)
     }
 }
 
-#define PDWT_CHECK_LAUNCH3() PDWT_HIP_TRY(hipGetLastError())
-
 template <typename T, int HL>
 static int launch_level(int dir, int pass, const XYJob<T>& xy, const ZJob<T>& zj, int nz, const Taps2<T>& taps)
 {
     if (pass == 0) {  // x-y
         const bool fwd = dir == 0;
         const size_t lds = fwd ? tile_fwd_lds<T, HL>(false) : tile_inv_lds<T, HL>(true);
-        const void* kfn = fwd ? (const void*)k_fwd_xy<T, HL> : (const void*)k_inv_xy<T, HL>;
-        if (lds > 64 * 1024)
-            if (const int rc = lds_opt_in_ptr(kfn); rc != PDWT_OK) return rc;
         const dim3 grid = fwd ? dim3(idiv_up(xy.hx, TFX), idiv_up(xy.hy, TFY), nz) : dim3(idiv_up(xy.nx, TIX), idiv_up(xy.ny, TIY), nz);
-        if (fwd) hipLaunchKernelGGL((k_fwd_xy<T, HL>), grid, dim3(kTileThreads), lds, stream(), xy, taps);
-        else hipLaunchKernelGGL((k_inv_xy<T, HL>), grid, dim3(kTileThreads), lds, stream(), xy, taps);
-    } else {  // z
-        const dim3 grid(idiv_up(zj.plane, kZThreads), idiv_up(zj.nout, ZC), 4);
-        if (dir == 0) hipLaunchKernelGGL((k_ana_z<T, HL>), grid, dim3(kZThreads), 0, stream(), zj, taps);
-        else hipLaunchKernelGGL((k_syn_z<T, HL>), grid, dim3(kZThreads), 0, stream(), zj, taps);
+        return launch_lds(fwd ? k_fwd_xy<T, HL> : k_inv_xy<T, HL>, grid, dim3(kTileThreads), lds, xy, taps);
     }
-    PDWT_CHECK_LAUNCH3();
-    return PDWT_OK;
+    const dim3 grid(idiv_up(zj.plane, kZThreads), idiv_up(zj.nout, ZC), 4);  // z
+    return launch_lds(dir == 0 ? k_ana_z<T, HL> : k_syn_z<T, HL>, grid, dim3(kZThreads), 0, zj, taps);
 }
 
 template <typename T>

@@ -20,10 +20,9 @@
 
 namespace pdwt {
 
-constexpr size_t kExt1dLdsMax = 160 * 1024;   // the hard ceiling of a workgroup
+constexpr size_t kExt1dLdsMax = 160 * 1024;   // the hard ceiling of a workgroup (a literal: tests/test_newer_bank_matrix_cpu.py reads it)
 constexpr size_t kExt1dPackLds = 32 * 1024;   // packs of several rows stay below this
-
-__device__ __forceinline__ void ext1d_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
+static_assert(kExt1dLdsMax == kLdsMax, "one ceiling for every whole-signal kernel");
 
 template <typename T, int HL>
 __global__ __launch_bounds__(kExt1dThreads) void k_ext1d_fwd_fused(const T* __restrict__ src, Ext1dBands<T> b, int Nr, int R, int mode, Taps2<T> taps)
@@ -37,17 +36,17 @@ __global__ __launch_bounds__(kExt1dThreads) void k_ext1d_fwd_fused(const T* __re
     T* cur = reinterpret_cast<T*>(smem);           // R lines of stride(n_0), later of n_2, n_4, ...
     T* nxt = cur + (size_t)R * cs;                 // R lines of stride(n_1), later of n_3, ...
     ext1d_stage_rows<T, NT>(cur, cs, off, src + row0 * (size_t)n, rows, n, tid);
-    ext1d_lds_barrier();
+    lds_barrier();
     ext1d_fill_halo<T, NT>(cur, cs, off, rows, n, HL, mode, tid);
-    ext1d_lds_barrier();
+    lds_barrier();
     for (int lev = 1; lev <= b.nlev; lev++) {
         const int N = b.n[lev], ns = ext1d_stride(N, HL);
         const bool last = lev == b.nlev;
         ext1d_fwd_level<T, HL, NT>(cur, cs, nxt, ns, off, rows, n, HL, taps, b.p[lev] + row0 * (size_t)N, last ? b.p[0] + row0 * (size_t)N : nullptr, tid);
         if (last) break;
-        ext1d_lds_barrier();
+        lds_barrier();
         ext1d_fill_halo<T, NT>(nxt, ns, off, rows, N, HL, mode, tid);
-        ext1d_lds_barrier();
+        lds_barrier();
         T* t = cur;
         cur = nxt, nxt = t;
         n = N, cs = ns;
@@ -71,13 +70,13 @@ __global__ __launch_bounds__(kExt1dThreads) void k_ext1d_inv_fused(T* __restrict
     for (int lev = L; lev >= 1; lev--) {
         const int N = b.n[lev], n = b.n[lev - 1], st = ext1d_ru4(N);
         ext1d_stage_rows<T, NT>(d, st, 0, b.p[lev] + row0 * (size_t)N, rows, N, tid);
-        ext1d_lds_barrier();
+        lds_barrier();
         if (lev == 1) {
             ext1d_inv_level<T, HL, NT>(a, st, d, st, dst + row0 * (size_t)n, n, rows, n, HL, taps, tid);
             break;
         }
         ext1d_inv_level<T, HL, NT>(a, st, d, st, o, ext1d_ru4(n), rows, n, HL, taps, tid);
-        ext1d_lds_barrier();  // the output is complete and every read of a and d is done before d is staged again
+        lds_barrier();  // the output is complete and every read of a and d is done before d is staged again
         T* t = a;
         a = o, o = t;
     }
@@ -92,7 +91,7 @@ __global__ __launch_bounds__(kExt1dThreads) void k_ext1d_fwd(const T* __restrict
     const unsigned row = blockIdx.x / (unsigned)tiles, tile = blockIdx.x - row * (unsigned)tiles;
     const int i0 = (int)tile * kExt1dTile, cnt = N - i0 < kExt1dTile ? N - i0 : kExt1dTile;
     ext1d_stage_window<T, kExt1dThreads>(win, src + (size_t)row * n, n, 2 * i0 + 2 - hlen, 2 * cnt + hlen - 2, mode, tid);
-    ext1d_lds_barrier();
+    lds_barrier();
     const size_t o = (size_t)row * N + i0;
     ext1d_fwd_tile<T, kExt1dThreads>(win, cnt, hlen, taps, a + o, d + o, tid);
 }
@@ -113,7 +112,7 @@ __global__ __launch_bounds__(kExt1dThreads) void k_ext1d_inv(T* __restrict__ dst
         wa[k] = a[o + k];
         wd[k] = d[o + k];
     }
-    ext1d_lds_barrier();
+    lds_barrier();
     ext1d_inv_tile<T, kExt1dThreads>(wa, wd, cntp, n - 2 * p0, hlen, taps, dst + (size_t)row * n + 2 * p0, tid);
 }
 

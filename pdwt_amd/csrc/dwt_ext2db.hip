@@ -8,7 +8,7 @@
 //                       (V, D) are staged per level (at most two child bands resident), the last level writes the image.
 //   per level           images that do not fit LDS, and the level entries of the C ABI: the x-y tile kernels of dwt_ext3d.hip with the
 //                       images as the planes (run_ext3_xy: no kernel of its own), one launch per level and direction.
-// The stages of the fused kernels are the functions of dwt_ext2db.hpp; all three forms (and a loop over BoundaryWavelets instances)
+// The pipelines of the fused kernels are the functions of dwt_ext2db.hpp, their stages those of image_stages.hpp; all three forms (and a loop over BoundaryWavelets instances)
 // compute the same bits.  Barriers between LDS stages are LDS-only (lgkmcnt), so the detail stores of a level are not waited for.
 //
 // Workgroup size 512.  An image above 80 KiB of LDS has the compute unit to itself; 256 threads would leave one wave per SIMD to hide
@@ -24,12 +24,7 @@
 
 namespace pdwt {
 
-constexpr size_t kExt2dbLdsMax = 160 * 1024;  // the hard ceiling of a workgroup
-constexpr int kExt2dbMaxBatch = 65535;        // the images are grid.z of the per-level kernels
-
-struct Ext2dbLdsBarrier {
-    __device__ __forceinline__ void operator()() const { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-};
+constexpr int kExt2dbMaxBatch = 65535;  // the images are grid.z of the per-level kernels
 
 template <typename T, int HL>
 __global__ __launch_bounds__(kExt2dbThreads) void k_ext2db_fwd_fused(const T* __restrict__ src, Ext2dbBands<T> b, int mode, Taps2<T> taps)
@@ -39,7 +34,7 @@ __global__ __launch_bounds__(kExt2dbThreads) void k_ext2db_fwd_fused(const T* __
     T* rb = img + b.nr[0] * b.nc[0];                           // [2][Nr][N_c1]: row pass lo | hi
     int* cmap = reinterpret_cast<int*>(rb + 2 * b.nr[0] * b.nc[1]);
     int* rmap = cmap + 2 * b.nc[1] + HL - 2;
-    ext2db_fwd_image<T, HL, kExt2dbThreads>(img, rb, cmap, rmap, src, b, (size_t)blockIdx.x, mode, taps, (int)threadIdx.x, Ext2dbLdsBarrier());
+    ext2db_fwd_image<T, HL, kExt2dbThreads>(img, rb, cmap, rmap, src, b, (size_t)blockIdx.x, mode, taps, (int)threadIdx.x, LdsBarrier());
 }
 
 template <typename T, int HL>
@@ -50,7 +45,7 @@ __global__ __launch_bounds__(kExt2dbThreads) void k_ext2db_inv_fused(T* __restri
     T* ra = reinterpret_cast<T*>(smem);  // the approximation, then V
     T* rd = ra + cap;                    // H, then D
     T* cb = rd + cap;                    // [2][Nr][N_c1]
-    ext2db_inv_image<T, HL, kExt2dbThreads>(ra, rd, cb, dst, b, (size_t)blockIdx.x, taps, (int)threadIdx.x, Ext2dbLdsBarrier());
+    ext2db_inv_image<T, HL, kExt2dbThreads>(ra, rd, cb, dst, b, (size_t)blockIdx.x, taps, (int)threadIdx.x, LdsBarrier());
 }
 
 // ---- geometry and the plan (host, no device) ------------------------------------------------------------------------------------------
@@ -94,7 +89,7 @@ static Ext2dbPlan ext2db_plan(int Nr, int Nc, int hlen, int levels, size_t elem)
     Ext2dbPlan p;
     p.lds_fwd = (in_max + rb_max) * elem + tab * sizeof(int);
     p.lds_inv = (2 * band_max + rb_max) * elem;
-    p.fused = std::max(p.lds_fwd, p.lds_inv) <= kExt2dbLdsMax;
+    p.fused = std::max(p.lds_fwd, p.lds_inv) <= kLdsMax;
     return p;
 }
 
@@ -137,20 +132,14 @@ static int ext2db_inverse_level(T* dst, const T* a, const T* h, const T* v, cons
 template <typename T, int HL>
 static int launch_ext2db_fwd_fused(const T* src, const Ext2dbBands<T>& b, int B, int mode, const Ext2dbPlan& p, const Taps2<T>& taps)
 {
-    if (p.lds_fwd > 64 * 1024)
-        if (const int rc = lds_opt_in_ptr((const void*)k_ext2db_fwd_fused<T, HL>); rc != PDWT_OK) return rc;
-    hipLaunchKernelGGL((k_ext2db_fwd_fused<T, HL>), dim3(B), dim3(kExt2dbThreads), p.lds_fwd, stream(), src, b, mode, taps);
-    PDWT_HIP_TRY(hipGetLastError());
-    return PDWT_EXT2DB_FUSED;
+    const int rc = launch_lds(k_ext2db_fwd_fused<T, HL>, dim3(B), dim3(kExt2dbThreads), p.lds_fwd, src, b, mode, taps);
+    return rc == PDWT_OK ? PDWT_EXT2DB_FUSED : rc;
 }
 template <typename T, int HL>
 static int launch_ext2db_inv_fused(T* dst, const Ext2dbBands<T>& b, int B, const Ext2dbPlan& p, const Taps2<T>& taps)
 {
-    if (p.lds_inv > 64 * 1024)
-        if (const int rc = lds_opt_in_ptr((const void*)k_ext2db_inv_fused<T, HL>); rc != PDWT_OK) return rc;
-    hipLaunchKernelGGL((k_ext2db_inv_fused<T, HL>), dim3(B), dim3(kExt2dbThreads), p.lds_inv, stream(), dst, b, taps);
-    PDWT_HIP_TRY(hipGetLastError());
-    return PDWT_EXT2DB_FUSED;
+    const int rc = launch_lds(k_ext2db_inv_fused<T, HL>, dim3(B), dim3(kExt2dbThreads), p.lds_inv, dst, b, taps);
+    return rc == PDWT_OK ? PDWT_EXT2DB_FUSED : rc;
 }
 
 // The approximation stack of level l (1 .. L - 1) of the per-level path: the halves of d_tmp in turn (each B x N_r1 x N_c1 elements),

@@ -1,7 +1,10 @@
-// dwt_ext2db.hpp -- the stages of the fused kernels of the batched 2-D transform with signal-extension boundary modes (dwt_ext2db.hip;
-// include/pdwt_hip.h "Batched 2-D DWT with boundary modes"): the whole pyramid of ONE image in the LDS of one workgroup.  As in
-// dwt_ext1d.hpp every stage takes the thread count as a template argument and the thread index as an argument and contains no barrier;
-// the two pipelines (ext2db_fwd_image / ext2db_inv_image) take the barrier as a functor.  The kernels pass the LDS-only barrier and
+// dwt_ext2db.hpp -- the pipelines of the fused kernels of the batched 2-D transform with signal-extension boundary modes (dwt_ext2db.hip;
+// include/pdwt_hip.h "Batched 2-D DWT with boundary modes"): the whole pyramid of ONE image in the LDS of one workgroup.  The copy-in,
+// the two items and the synthesis stages are those of image_stages.hpp, shared with the packets (wpt2db.hpp); the synthesis runs on the
+// extended line: no shift, centre or table, one line pair per call.  The two analysis loops and the table fill are written out here:
+// through the shared analysis stages the float32 kernels of up to 10 taps measured 2 to 4 % slower (image_stages.hpp).  Every stage takes the thread count as a
+// template argument and the thread index as an argument and contains no barrier; the two pipelines (ext2db_fwd_image /
+// ext2db_inv_image) take the barrier as a functor.  The kernels pass the LDS-only barrier and
 // NT = 512; a host program passes a no-op and NT = 1, tid = 0 and runs whole pipelines on the CPU under a sanitizer.
 //
 // Values.  The operation sequence is that of the tile kernels of dwt_ext.hpp, so the results are the same bits: forward rows first with
@@ -17,7 +20,7 @@
 // fills cb[0]; then V and D are staged over the two (at most two child bands are resident at a time) and fill cb[1]; row synthesis
 // writes the nr x nc result into ra, the next level's approximation, or, at level 1, to the image in HBM.
 #pragma once
-#include "dwt_ext1d.hpp"
+#include "image_stages.hpp"
 
 namespace pdwt {
 
@@ -31,55 +34,12 @@ struct Ext2dbBands {
     int nlev;
 };
 
-// n contiguous elements src -> dst (LDS): 16-byte loads and stores where src is aligned (dst is: every LDS region starts on 16 bytes),
-// the tail element-wise
-template <typename T, int NT>
-__host__ __device__ __forceinline__ void ext2db_copy_in(T* dst, const T* __restrict__ src, int n, int tid)
-{
-    using V = typename Ext1dVec<T>::v16;
-    constexpr int NV = Ext1dVec<T>::NV;
-    int done = 0;
-    if ((reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0) {
-        const int nch = n / NV;
-        for (int e = tid; e < nch; e += NT) reinterpret_cast<V*>(dst)[e] = reinterpret_cast<const V*>(src)[e];
-        done = nch * NV;
-    }
-    for (int e = done + tid; e < n; e += NT) dst[e] = src[e];
-}
-
 // map[k] = the sample that xe[k + 2 - F] repeats, k = 0 .. 2 * half + F - 3: the windows of the `half` positions of a line of n samples
 template <int NT>
 __host__ __device__ __forceinline__ void ext2db_fill_map(int* map, int n, int half, int F, int mode, int tid)
 {
     const int cnt = 2 * half + F - 2;
     for (int k = tid; k < cnt; k += NT) map[k] = ext_index(k + 2 - F, n, mode);
-}
-
-// The 2 * HL taps stay in scalar registers for the short banks only (up to 10 taps float32, 4 float64): next to the shapes, the band
-// pointers and the loop state of a whole pyramid a longer bank spills scalar registers.  Longer banks index the taps through the opaque
-// zero of dwt_ext.hpp, so that they are loaded where they are used.
-template <typename T, int HL>
-constexpr bool ext2db_opaque_taps() { return HL * sizeof(T) > 40; }
-
-// (lo, hi) of one position: `get(j)` is sample j of its window, j = 0 .. HL-1 (tap HL-1-j on sample j)
-template <typename T, int HL, typename Get>
-__host__ __device__ __forceinline__ void ext2db_fwd_item(Get get, const Taps2<T>& taps, T& lo, T& hi)
-{
-    const int z0 = ext2db_opaque_taps<T, HL>() ? ext1d_zero() : 0;
-    T sl = T(0), sh = T(0);
-    auto step = [&](int j) {
-        const T v = get(j);
-        sl = ext1d_fma(v, taps.a[HL - 1 - j + z0], sl);
-        sh = ext1d_fma(v, taps.b[HL - 1 - j + z0], sh);
-    };
-    if constexpr (ext2db_opaque_taps<T, HL>()) {
-#pragma unroll 8
-        for (int j = 0; j < HL; j++) step(j);
-    } else {
-#pragma unroll
-        for (int j = 0; j < HL; j++) step(j);
-    }
-    lo = sl, hi = sh;
 }
 
 // Analysis along the rows of in[nr][nc]: hc positions per row, low pass into rb[0][nr][hc], high pass into rb[1][nr][hc].
@@ -94,10 +54,10 @@ __host__ __device__ __forceinline__ void ext2db_rows_analysis(const T* in, T* rb
         T lo, hi;
         if (s0 >= 0 && 2 * ox + 1 < nc) {
             const T* p = row + s0;
-            ext2db_fwd_item<T, HL>([&](int j) { return p[j]; }, taps, lo, hi);
+            img_fwd_item<T, HL>([&](int j) { return p[j]; }, taps, lo, hi);
         } else {
             const int* m = cmap + 2 * ox;
-            ext2db_fwd_item<T, HL>([&](int j) { const int s = m[j]; return s < 0 ? T(0) : row[s]; }, taps, lo, hi);
+            img_fwd_item<T, HL>([&](int j) { const int s = m[j]; return s < 0 ? T(0) : row[s]; }, taps, lo, hi);
         }
         rb[e] = lo;
         rb[total + e] = hi;
@@ -120,10 +80,10 @@ __host__ __device__ __forceinline__ void ext2db_cols_analysis(const T* rb, const
         T lo, hi;
         if (s0 >= 0 && 2 * oy + 1 < nr) {
             const T* p = col + s0 * hc;
-            ext2db_fwd_item<T, HL>([&](int j) { return p[j * hc]; }, taps, lo, hi);
+            img_fwd_item<T, HL>([&](int j) { return p[j * hc]; }, taps, lo, hi);
         } else {
             const int* m = rmap + 2 * oy;
-            ext2db_fwd_item<T, HL>([&](int j) { const int s = m[j]; return s < 0 ? T(0) : col[s * hc]; }, taps, lo, hi);
+            img_fwd_item<T, HL>([&](int j) { const int s = m[j]; return s < 0 ? T(0) : col[s * hc]; }, taps, lo, hi);
         }
         if (xb) {
             gv[o] = lo;
@@ -142,7 +102,7 @@ __host__ __device__ __forceinline__ void ext2db_fwd_image(T* img, T* rb, int* cm
                                                           const Taps2<T>& taps, int tid, Bar bar)
 {
     const int L = b.nlev;
-    ext2db_copy_in<T, NT>(img, src + ib * ((size_t)b.nr[0] * b.nc[0]), b.nr[0] * b.nc[0], tid);
+    img_copy_in<T, NT>(img, src + ib * ((size_t)b.nr[0] * b.nc[0]), b.nr[0] * b.nc[0], tid);
     ext2db_fill_map<NT>(cmap, b.nc[0], b.nc[1], HL, mode, tid);
     bar();
     for (int lev = 1; lev <= L; lev++) {
@@ -161,86 +121,32 @@ __host__ __device__ __forceinline__ void ext2db_fwd_image(T* img, T* rb, int* cm
 }
 
 // ---- inverse --------------------------------------------------------------------------------------------------------------------------
-// (x0, x1) = samples 2p, 2p + 1 of a line from the coefficients pa[m * st], pd[m * st], m = 0 .. HL/2 - 1 (= a[p ..], d[p ..]): the sums of
-// ext1d_inv_item with a stride
-template <typename T, int HL>
-__host__ __device__ __forceinline__ void ext2db_inv_item(const T* pa, const T* pd, int st, const Taps2<T>& taps, T& x0, T& x1)
-{
-    const int z0 = ext2db_opaque_taps<T, HL>() ? ext1d_zero() : 0;
-    T ae = T(0), ao = T(0), de = T(0), dd = T(0);
-    auto step = [&](int m) {
-        const T ca = pa[m * st], cd = pd[m * st];
-        ae = ext1d_fma(ca, taps.a[HL - 2 - 2 * m + z0], ae);
-        ao = ext1d_fma(ca, taps.a[HL - 1 - 2 * m + z0], ao);
-        de = ext1d_fma(cd, taps.b[HL - 2 - 2 * m + z0], de);
-        dd = ext1d_fma(cd, taps.b[HL - 1 - 2 * m + z0], dd);
-    };
-    if constexpr (ext2db_opaque_taps<T, HL>()) {
-#pragma unroll 4
-        for (int m = 0; m < HL / 2; m++) step(m);
-    } else {
-#pragma unroll
-        for (int m = 0; m < HL / 2; m++) step(m);
-    }
-    x0 = ae + de, x1 = ao + dd;
-}
-
-// Synthesis along the columns of the pair a (column low), d (column high), both [hr][hc], into cb[nr][hc]; two rows per work item.  The
-// last coefficient read is row ((nr - 1) >> 1) + HL / 2 - 1 = hr - 1.
-template <typename T, int HL, int NT>
-__host__ __device__ __forceinline__ void ext2db_cols_synthesis(const T* a, const T* d, T* cb, int nr, int hc, const Taps2<T>& taps, int tid)
-{
-    const int total = ((nr + 1) >> 1) * hc;
-    for (int e = tid; e < total; e += NT) {
-        const int p = e / hc, cc = e - p * hc;
-        T x0, x1;
-        ext2db_inv_item<T, HL>(a + p * hc + cc, d + p * hc + cc, hc, taps, x0, x1);
-        cb[(2 * p) * hc + cc] = x0;
-        if (2 * p + 1 < nr) cb[(2 * p + 1) * hc + cc] = x1;
-    }
-}
-
-// Synthesis along the rows of cb0 (row low) and cb1 (row high), both [nr][hc], into out[nr][nc] (LDS or HBM); two samples per work item
-template <typename T, int HL, int NT>
-__host__ __device__ __forceinline__ void ext2db_rows_synthesis(const T* cb0, const T* cb1, T* out, int nr, int nc, int hc, const Taps2<T>& taps, int tid)
-{
-    const int P = (nc + 1) >> 1, total = nr * P;
-    for (int e = tid; e < total; e += NT) {
-        const int r = e / P, p = e - r * P;
-        T x0, x1;
-        ext2db_inv_item<T, HL>(cb0 + r * hc + p, cb1 + r * hc + p, 1, taps, x0, x1);
-        T* o = out + (size_t)r * nc + 2 * p;
-        o[0] = x0;
-        if (2 * p + 1 < nc) o[1] = x1;
-    }
-}
-
 // All levels of image `ib`, coarse to fine.  ra, rd: one band of the largest level each (nr[1] * nc[1] elements, rounded up to 16 bytes);
 // cb: 2 * Nr * nc[1].
 template <typename T, int HL, int NT, typename Bar>
 __host__ __device__ __forceinline__ void ext2db_inv_image(T* ra, T* rd, T* cb, T* __restrict__ dst, const Ext2dbBands<T>& b, size_t ib, const Taps2<T>& taps, int tid, Bar bar)
 {
     const int L = b.nlev;
-    ext2db_copy_in<T, NT>(ra, b.p[0] + ib * ((size_t)b.nr[L] * b.nc[L]), b.nr[L] * b.nc[L], tid);
+    img_copy_in<T, NT>(ra, b.p[0] + ib * ((size_t)b.nr[L] * b.nc[L]), b.nr[L] * b.nc[L], tid);
     for (int lev = L; lev >= 1; lev--) {
         const int nr = b.nr[lev - 1], nc = b.nc[lev - 1], hr = b.nr[lev], hc = b.nc[lev], per = hr * hc;
         const size_t o = ib * (size_t)per;
         T* const* d = b.p + 3 * (lev - 1) + 1;
         T* cb1 = cb + nr * hc;
-        ext2db_copy_in<T, NT>(rd, d[0] + o, per, tid);  // H  (rd was last read two barriers ago)
+        img_copy_in<T, NT>(rd, d[0] + o, per, tid);  // H  (rd was last read two barriers ago)
         bar();
-        ext2db_cols_synthesis<T, HL, NT>(ra, rd, cb, nr, hc, taps, tid);
+        img_cols_synthesis<T, HL, false, 1, NT>(ra, rd, 0, cb, nullptr, nullptr, 1, nr, hr, hc, taps, tid);
         bar();
-        ext2db_copy_in<T, NT>(ra, d[1] + o, per, tid);  // V
-        ext2db_copy_in<T, NT>(rd, d[2] + o, per, tid);  // D
+        img_copy_in<T, NT>(ra, d[1] + o, per, tid);  // V
+        img_copy_in<T, NT>(rd, d[2] + o, per, tid);  // D
         bar();
-        ext2db_cols_synthesis<T, HL, NT>(ra, rd, cb1, nr, hc, taps, tid);
+        img_cols_synthesis<T, HL, false, 1, NT>(ra, rd, 0, cb1, nullptr, nullptr, 1, nr, hr, hc, taps, tid);
         bar();
         if (lev == 1) {
-            ext2db_rows_synthesis<T, HL, NT>(cb, cb1, dst + ib * ((size_t)nr * nc), nr, nc, hc, taps, tid);
+            img_rows_synthesis<T, HL, false, 1, NT>(cb, dst + ib * ((size_t)nr * nc), nullptr, nullptr, 1, nr, nc, hc, taps, tid);
             break;
         }
-        ext2db_rows_synthesis<T, HL, NT>(cb, cb1, ra, nr, nc, hc, taps, tid);  // A_{lev-1}, complete at the barrier after the next H is staged
+        img_rows_synthesis<T, HL, false, 1, NT>(cb, ra, nullptr, nullptr, 1, nr, nc, hc, taps, tid);  // A_{lev-1}, complete at the barrier after the next H is staged
     }
 }
 

@@ -149,22 +149,14 @@ template <typename T, int HL>
 static int launch_ext3_xy(bool fwd, const Ext3XYJob<T>& xy, int nz, const Taps2<T>& taps)
 {
     const size_t lds = fwd ? tile_fwd_lds<T, HL>(true) : tile_inv_lds<T, HL>(false);
-    const void* kfn = fwd ? (const void*)k_ext3_fwd_xy<T, HL> : (const void*)k_ext3_inv_xy<T, HL>;
-    if (lds > 64 * 1024)
-        if (const int rc = lds_opt_in_ptr(kfn); rc != PDWT_OK) return rc;
-    if (fwd) hipLaunchKernelGGL((k_ext3_fwd_xy<T, HL>), dim3(idiv_up(xy.hc, TFX), idiv_up(xy.hr, TFY), nz), dim3(kTileThreads), lds, stream(), xy, taps);
-    else hipLaunchKernelGGL((k_ext3_inv_xy<T, HL>), dim3(idiv_up(xy.nc, TIX), idiv_up(xy.nr, TIY), nz), dim3(kTileThreads), lds, stream(), xy, taps);
-    PDWT_HIP_TRY(hipGetLastError());
-    return PDWT_OK;
+    const dim3 grid = fwd ? dim3(idiv_up(xy.hc, TFX), idiv_up(xy.hr, TFY), nz) : dim3(idiv_up(xy.nc, TIX), idiv_up(xy.nr, TIY), nz);
+    return launch_lds(fwd ? k_ext3_fwd_xy<T, HL> : k_ext3_inv_xy<T, HL>, grid, dim3(kTileThreads), lds, xy, taps);
 }
 template <typename T, int HL>
 static int launch_ext3_z(bool fwd, const Ext3ZJob<T>& zj, const Taps2<T>& taps)
 {
     const dim3 grid(idiv_up(zj.plane, kX3ZThreads), idiv_up(zj.nout, X3ZC), 4);
-    if (fwd) hipLaunchKernelGGL((k_ext3_ana_z<T, HL>), grid, dim3(kX3ZThreads), 0, stream(), zj, taps);
-    else hipLaunchKernelGGL((k_ext3_syn_z<T, HL>), grid, dim3(kX3ZThreads), 0, stream(), zj, taps);
-    PDWT_HIP_TRY(hipGetLastError());
-    return PDWT_OK;
+    return launch_lds(fwd ? k_ext3_ana_z<T, HL> : k_ext3_syn_z<T, HL>, grid, dim3(kX3ZThreads), 0, zj, taps);
 }
 
 // (external linkage: dwt_ext2db.hip runs the same instantiations on the images of a batch)

@@ -25,13 +25,10 @@
 
 namespace pdwt {
 
-constexpr size_t kAdjLdsMax = 160 * 1024;
 constexpr int kAdjThreads = 256;  // the fold kernel (the synthesis kernel: kTileThreads)
 constexpr int AFY = 32, AFX = 8;  // fold tile (samples)
 constexpr int kAdjMaxBatch = 65535;
 constexpr int kAdjMaxLev = 32;
-
-__device__ __forceinline__ void adj_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
 
 template <typename T>
 struct AdjJob {
@@ -115,7 +112,7 @@ __global__ __launch_bounds__(kExt1dThreads) void k_ext1d_adj(T* __restrict__ dst
     const int w = cntp + hlen / 2 - 1;
     ext1d_adj_stage<T, kExt1dThreads>(wa, a + (size_t)row * N, N, hlen, p0, w, tid);
     ext1d_adj_stage<T, kExt1dThreads>(wd, d + (size_t)row * N, N, hlen, p0, w, tid);
-    adj_lds_barrier();
+    lds_barrier();
     ext1d_adj_tile<T, kExt1dThreads>(wa, wd, p0, cntp, n, hlen, taps, dst + (size_t)row * n, halo ? halo + (size_t)row * adj_halo_len(n, hlen) : nullptr, tid);
 }
 
@@ -129,7 +126,7 @@ __global__ __launch_bounds__(kExt1dThreads) void k_ext1d_adj_fold(T* __restrict_
     const T* hl = halo + row0 * (size_t)H;
     __shared__ int hmap[2 * PDWT_MAX_FILTER_WIDTH];
     ext1d_halo_map<kExt1dThreads>(hmap, n, F, mode, (int)threadIdx.x);
-    adj_lds_barrier();
+    lds_barrier();
     ext1d_fold_halo<T, kExt1dThreads>(dst + row0 * (size_t)n, n, hl, hl + (F - 2), H, hmap, rows, n, F, (int)threadIdx.x);
 }
 
@@ -164,12 +161,12 @@ __global__ __launch_bounds__(kExt1dThreads) void k_ext1d_adj_fused(T* __restrict
         ext1d_zero_cells<T, NT>(db, dstr, dof - pad, pad, rows, tid);
         ext1d_zero_cells<T, NT>(db, dstr, dof + N, pad, rows, tid);
         ext1d_halo_map<NT>(hmap, n, HL, mode, tid);  // (the fold of the level before is behind a barrier)
-        adj_lds_barrier();
+        lds_barrier();
         T* out = buf[(lev - 1) & 1];
         ext1d_adj_level<T, HL, NT>(cur + off - pad, cs, db + dof - pad, dstr, out + off - (HL - 2), os, rows, N, HL, taps, tid);
-        adj_lds_barrier();
+        lds_barrier();
         ext1d_fold_halo<T, NT>(out + off, os, out + off - (HL - 2), out + off + n, os, hmap, rows, n, HL, tid);
-        adj_lds_barrier();
+        lds_barrier();
         if (lev == 1) {
             ext1d_store_rows<T, NT>(dst + row0 * (size_t)n, out, os, off, rows, n, tid);
             break;
@@ -225,7 +222,7 @@ static Adj1Plan adj1_plan(int nc, int hlen, int levels, size_t elem)
 {
     const int n1 = ext_half(nc, hlen);
     const size_t row = ((size_t)ext1d_stride(nc, hlen) + ext1d_stride(n1, hlen) + adj1d_dstride(n1, hlen)) * elem;
-    Adj1Plan p{pdwt_ext1d_fused(nc, hlen, levels, (int)elem) == 1 && row + kAdj1MapBytes <= kAdjLdsMax, 1, row + kAdj1MapBytes};
+    Adj1Plan p{pdwt_ext1d_fused(nc, hlen, levels, (int)elem) == 1 && row + kAdj1MapBytes <= kLdsMax, 1, row + kAdj1MapBytes};
     if (!p.fused) return p;
     int R = 1;
     while (R < 64 && R * n1 < kExt1dThreads && 2 * R * row <= 32 * 1024) R *= 2;
@@ -238,12 +235,8 @@ template <typename T, int HL>
 static int launch_adj_syn(const AdjJob<T>& job, int B, const Taps2<T>& taps)
 {
     constexpr size_t lds = tile_inv_lds<T, HL>(false);
-    if (lds > 64 * 1024)
-        if (const int rc = lds_opt_in_ptr((const void*)k_ext_adj_syn<T, HL>); rc != PDWT_OK) return rc;
     const dim3 grid(idiv_up(adj_ext_len(job.nc, HL), TIX), idiv_up(adj_ext_len(job.nr, HL), TIY), B);
-    hipLaunchKernelGGL((k_ext_adj_syn<T, HL>), grid, dim3(kTileThreads), lds, stream(), job, taps);
-    PDWT_HIP_TRY(hipGetLastError());
-    return PDWT_OK;
+    return launch_lds(k_ext_adj_syn<T, HL>, grid, dim3(kTileThreads), lds, job, taps);
 }
 
 // (external linkage: dwt_ext3d_adj.hip runs it on the nz planes of a volume)
@@ -313,11 +306,8 @@ static int adj1_forward_level(T* dst, const T* a, const T* d, int nr, int nc, in
 template <typename T, int HL>
 static int launch_adj1_fused(T* dst, const Ext1dBands<T>& b, int nr, int mode, const Adj1Plan& p, const Taps2<T>& taps)
 {
-    if (p.lds > 64 * 1024)
-        if (const int rc = lds_opt_in_ptr((const void*)k_ext1d_adj_fused<T, HL>); rc != PDWT_OK) return rc;
-    hipLaunchKernelGGL((k_ext1d_adj_fused<T, HL>), dim3(idiv_up(nr, p.R)), dim3(kExt1dThreads), p.lds, stream(), dst, b, nr, p.R, mode, taps);
-    PDWT_HIP_TRY(hipGetLastError());
-    return PDWT_EXT1D_FUSED;
+    const int rc = launch_lds(k_ext1d_adj_fused<T, HL>, dim3(idiv_up(nr, p.R)), dim3(kExt1dThreads), p.lds, dst, b, nr, p.R, mode, taps);
+    return rc == PDWT_OK ? PDWT_EXT1D_FUSED : rc;
 }
 
 template <typename T>

@@ -253,19 +253,11 @@ static int swt_launch(int dir, int pass, const SXYJob<T>& xy, const SZJob<T>& zj
     if (pass == 0) {  // x-y
         const bool fwd = dir == 0;
         const size_t lds = fwd ? swt_fwd_xy_lds<T, HL>() : swt_inv_xy_lds<T, HL>();
-        const void* kfn = fwd ? (const void*)k_swt_fwd_xy<T, HL> : (const void*)k_swt_inv_xy<T, HL>;
-        if (lds > 64 * 1024)
-            if (const int rc = lds_opt_in_ptr(kfn); rc != PDWT_OK) return rc;
         const dim3 grid((unsigned)xy.tiles_x * (unsigned)tiles_of(xy.ny, xy.f, STY), 1, nz);
-        if (fwd) hipLaunchKernelGGL((k_swt_fwd_xy<T, HL>), grid, dim3(kSXYThreads), lds, stream(), xy, taps);
-        else hipLaunchKernelGGL((k_swt_inv_xy<T, HL>), grid, dim3(kSXYThreads), lds, stream(), xy, taps);
-    } else {  // z
-        const dim3 grid(idiv_up(zj.plane, kSZThreads), tiles_of(zj.n, zj.f, swt_zc<T, HL>()), 4);
-        if (dir == 0) hipLaunchKernelGGL((k_swt_ana_z<T, HL>), grid, dim3(kSZThreads), 0, stream(), zj, taps);
-        else hipLaunchKernelGGL((k_swt_syn_z<T, HL>), grid, dim3(kSZThreads), 0, stream(), zj, taps);
+        return launch_lds(fwd ? k_swt_fwd_xy<T, HL> : k_swt_inv_xy<T, HL>, grid, dim3(kSXYThreads), lds, xy, taps);
     }
-    PDWT_HIP_TRY(hipGetLastError());
-    return PDWT_OK;
+    const dim3 grid(idiv_up(zj.plane, kSZThreads), tiles_of(zj.n, zj.f, swt_zc<T, HL>()), 4);  // z
+    return launch_lds(dir == 0 ? k_swt_ana_z<T, HL> : k_swt_syn_z<T, HL>, grid, dim3(kSZThreads), 0, zj, taps);
 }
 
 template <typename T>

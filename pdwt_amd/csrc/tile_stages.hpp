@@ -13,7 +13,7 @@
 // and read the taps straight from the kernel argument; behind a function that takes the taps by reference the compiler loads all
 // 2 * HL taps at the kernel's entry, and the float64 banks of 22 taps and more spill SGPRs); swt3d.hip (sublattice addressing, chunked
 // tap reloads in fma_taps2, an inverse that stages one x band at a time); the whole-image-in-LDS kernels with run-time geometry
-// (dwt_ext2db.hpp, wpt2db.hpp, dwt_ext1d.hpp, wpt1d.hpp); k_ext3_adj_z (dwt_ext3d_adj.hpp); the Haar and cost kernels of wpt2d.hip.
+// (their 2-D stages are shared in image_stages.hpp, the 1-D ones in dwt_ext1d.hpp / wpt1d.hpp); k_ext3_adj_z (dwt_ext3d_adj.hpp); the Haar and cost kernels of wpt2d.hip.
 #pragma once
 #include "vol3d.hpp"
 

@@ -19,26 +19,18 @@
 // Row packing: R = the power of two >= 256 / div2(Nc) (every thread has a position at depth 1), at most 64 and as many as fit 32 KiB.
 // Budget rule (needs no device): fused when that region, for ONE row, fits 160 KiB in both directions (pdwt_wp1_fused).
 #include <algorithm>
-#include <vector>
 
 #include "wpt1d.hpp"
 
 namespace pdwt {
 
-constexpr size_t kWp1LdsMax = 160 * 1024;  // the hard ceiling of a workgroup
 constexpr size_t kWp1PackLds = 32 * 1024;  // packs of several rows stay below this
-
-__device__ __forceinline__ void wp1_lds_barrier() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-
-struct Wp1LdsSync {
-    __device__ __forceinline__ void operator()() const { wp1_lds_barrier(); }
-};
 
 template <typename T, int HL>
 __global__ __launch_bounds__(kWp1Threads) void k_wp1_fwd_fused(const T* __restrict__ src, Wp1Levels<T> lv, int Nr, int R, int region, Taps2<T> taps)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    wp1_fwd_fused_block<T, HL, kWp1Threads>(reinterpret_cast<T*>(smem), region, src, lv, Nr, R, blockIdx.x, taps, threadIdx.x, Wp1LdsSync());
+    wp1_fwd_fused_block<T, HL, kWp1Threads>(reinterpret_cast<T*>(smem), region, src, lv, Nr, R, blockIdx.x, taps, threadIdx.x, LdsBarrier());
 }
 
 template <typename T, int HL>
@@ -46,7 +38,7 @@ __global__ __launch_bounds__(kWp1Threads) void k_wp1_inv_fused(T* __restrict__ d
                                                                Taps2<T> taps)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    wp1_inv_fused_block<T, HL, kWp1Threads>(reinterpret_cast<T*>(smem), region, dst, lv, state, Nr, R, blockIdx.x, taps, threadIdx.x, Wp1LdsSync());
+    wp1_inv_fused_block<T, HL, kWp1Threads>(reinterpret_cast<T*>(smem), region, dst, lv, state, Nr, R, blockIdx.x, taps, threadIdx.x, LdsBarrier());
 }
 
 // src: (nr, nodes, n); dst: (nr, 2 * nodes, N).  blockIdx.x = (row * nodes + parent) * tiles + tile
@@ -54,7 +46,7 @@ template <typename T>
 __global__ __launch_bounds__(kWp1Threads) void k_wp1_fwd(const T* __restrict__ src, T* __restrict__ dst, int n, int N, int tiles, int hlen, Taps2<T> taps)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    wp1_fwd_level_block<T, kWp1Threads>(reinterpret_cast<T*>(smem), src, dst, n, N, tiles, hlen, blockIdx.x, taps, threadIdx.x, Wp1LdsSync());
+    wp1_fwd_level_block<T, kWp1Threads>(reinterpret_cast<T*>(smem), src, dst, n, N, tiles, hlen, blockIdx.x, taps, threadIdx.x, LdsBarrier());
 }
 
 // par: (nr, nodes, n); child: (nr, 2 * nodes, N).  blockIdx.x = (row * count + position in the list) * tiles + tile; a parent whose
@@ -64,7 +56,7 @@ __global__ __launch_bounds__(kWp1Threads) void k_wp1_inv(T* __restrict__ par, co
                                                          const unsigned char* __restrict__ st, int tiles, int hlen, Taps2<T> taps)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-    wp1_inv_level_block<T, kWp1Threads>(reinterpret_cast<T*>(smem), par, child, n, N, nodes, list, count, st, tiles, hlen, blockIdx.x, taps, threadIdx.x, Wp1LdsSync());
+    wp1_inv_level_block<T, kWp1Threads>(reinterpret_cast<T*>(smem), par, child, n, N, nodes, list, count, st, tiles, hlen, blockIdx.x, taps, threadIdx.x, LdsBarrier());
 }
 
 // ---- moments ------------------------------------------------------------------------------------------------------------------------
@@ -120,20 +112,13 @@ __global__ __launch_bounds__(kWp1Threads) void k_wp1_thresh(T* __restrict__ x, u
 }
 
 // ---- geometry and the plan of the fused path (host, no device) ----------------------------------------------------------------------
-static bool wp1_bank_ok(int hlen) { return hlen >= 2 && hlen <= PDWT_MAX_FILTER_WIDTH && !(hlen & 1); }
-static int wp1_ilog2(int v)
-{
-    int l = 0;
-    while (v > 1) v >>= 1, l++;
-    return l;
-}
 // the clamped depth (0: too small or a bad size / bank) and n_0 .. n_L
 static int wp1_geometry(int nc, int hlen, int levels, int* n)
 {
-    if (nc < 1 || nc > (1 << 30) || !wp1_bank_ok(hlen)) return 0;
+    if (nc < 1 || nc > (1 << 30) || !packet_bank_ok(hlen)) return 0;
     if (levels < 1) levels = 1;
     const int q = nc / (hlen - 1);
-    int lmax = q >= 1 ? wp1_ilog2(q) : 0;
+    int lmax = q >= 1 ? packet_ilog2(q) : 0;
     if (lmax > kWp1MaxLev) lmax = kWp1MaxLev;
     if (levels > lmax) levels = lmax;
     if (n)
@@ -162,7 +147,7 @@ static Wp1Plan wp1_plan(int nc, int hlen, int L, size_t elem)
     for (int l = 0; l + 1 <= L - 1; l++) fwd = std::max(fwd, fline(l) + fline(l + 1));
     for (int l = 1; l + 1 <= L; l++) inv = std::max(inv, iline(l) + iline(l + 1));
     fwd = (fwd + 3) & ~(size_t)3, inv = (inv + 3) & ~(size_t)3;  // (a multiple of 16 bytes in either precision)
-    Wp1Plan p{std::max(fwd, inv) * elem <= kWp1LdsMax, 1, 1, fwd, inv};
+    Wp1Plan p{std::max(fwd, inv) * elem <= kLdsMax, 1, 1, fwd, inv};
     if (!p.fused) return p;
     const int n1 = wp1_div2(nc);
     auto pack = [&](size_t row) {
@@ -191,7 +176,7 @@ static bool wp1_fill_levels(Wp1Levels<T>& lv, T* const* nodes, int nc, int L)
 template <typename T>
 static int wp1_forward_level(const T* par, T* child, int nr, int nnodes, int n, const typename FiltersOf<T>::type* f)
 {
-    if (!par || !child || !f || !wp1_bank_ok(f->hlen) || nnodes < 1 || nnodes > (1 << kWp1MaxLev) || n < 1) return PDWT_EINVAL;
+    if (!par || !child || !f || !packet_bank_ok(f->hlen) || nnodes < 1 || nnodes > (1 << kWp1MaxLev) || n < 1) return PDWT_EINVAL;
     const int N = wp1_div2(n), tiles = idiv_up(N, kWp1Tile);
     if (!wp1_level_ok(nr, nnodes, n) || (unsigned long long)nr * nnodes * tiles >= (1ull << 31)) return PDWT_EINVAL;
     const size_t lds = sizeof(T) * (2 * kWp1Tile + PDWT_MAX_FILTER_WIDTH);
@@ -204,7 +189,7 @@ template <typename T>
 static int wp1_inverse_level(T* par, const T* child, int nr, int nnodes, int n, const int* d_list, int count, const unsigned char* d_state,
                              const typename FiltersOf<T>::type* f)
 {
-    if (!par || !child || !f || !wp1_bank_ok(f->hlen) || nnodes < 1 || nnodes > (1 << kWp1MaxLev) || n < 1) return PDWT_EINVAL;
+    if (!par || !child || !f || !packet_bank_ok(f->hlen) || nnodes < 1 || nnodes > (1 << kWp1MaxLev) || n < 1) return PDWT_EINVAL;
     if (!d_list) count = nnodes;
     if (count < 1 || count > nnodes) return PDWT_EINVAL;
     const int N = wp1_div2(n), tiles = idiv_up(wp1_pairs(n, f->hlen), kWp1Tile);
@@ -220,21 +205,15 @@ template <typename T, int HL>
 static int launch_wp1_fwd_fused(const T* src, const Wp1Levels<T>& lv, int nr, const Wp1Plan& p, const Taps2<T>& taps)
 {
     const size_t lds = (size_t)p.R_fwd * p.region_fwd * sizeof(T);
-    if (lds > 64 * 1024)
-        if (const int rc = lds_opt_in_ptr((const void*)k_wp1_fwd_fused<T, HL>); rc != PDWT_OK) return rc;
-    hipLaunchKernelGGL((k_wp1_fwd_fused<T, HL>), dim3(idiv_up(nr, p.R_fwd)), dim3(kWp1Threads), lds, stream(), src, lv, nr, p.R_fwd, (int)(p.R_fwd * p.region_fwd), taps);
-    PDWT_HIP_TRY(hipGetLastError());
-    return PDWT_WP1_FUSED;
+    const int rc = launch_lds(k_wp1_fwd_fused<T, HL>, dim3(idiv_up(nr, p.R_fwd)), dim3(kWp1Threads), lds, src, lv, nr, p.R_fwd, (int)(p.R_fwd * p.region_fwd), taps);
+    return rc == PDWT_OK ? PDWT_WP1_FUSED : rc;
 }
 template <typename T, int HL>
 static int launch_wp1_inv_fused(T* dst, const Wp1Levels<T>& lv, const unsigned char* d_state, int nr, const Wp1Plan& p, const Taps2<T>& taps)
 {
     const size_t lds = (size_t)p.R_inv * p.region_inv * sizeof(T);
-    if (lds > 64 * 1024)
-        if (const int rc = lds_opt_in_ptr((const void*)k_wp1_inv_fused<T, HL>); rc != PDWT_OK) return rc;
-    hipLaunchKernelGGL((k_wp1_inv_fused<T, HL>), dim3(idiv_up(nr, p.R_inv)), dim3(kWp1Threads), lds, stream(), dst, lv, d_state, nr, p.R_inv, (int)(p.R_inv * p.region_inv), taps);
-    PDWT_HIP_TRY(hipGetLastError());
-    return PDWT_WP1_FUSED;
+    const int rc = launch_lds(k_wp1_inv_fused<T, HL>, dim3(idiv_up(nr, p.R_inv)), dim3(kWp1Threads), lds, dst, lv, d_state, nr, p.R_inv, (int)(p.R_inv * p.region_inv), taps);
+    return rc == PDWT_OK ? PDWT_WP1_FUSED : rc;
 }
 
 template <typename T>
@@ -324,29 +303,9 @@ int pdwt_wp1_frequency_order(int depth, int* out)
 }
 int pdwt_wp1_state_table(int levels, const int* depth, const int* idx, int n, unsigned char* out)
 {
-    if (levels < 1 || levels > kWp1MaxLev || !depth || !idx || !out || n < 1) return PDWT_EINVAL;
-    const int total = (2 << levels) - 1;
-    std::vector<unsigned char> leaf((size_t)1 << levels, 0);
-    for (int k = 0; k < total; k++) out[k] = WP1_SKIP;
-    for (int k = 0; k < n; k++) {
-        const int d = depth[k], i = idx[k];
-        if (d < 0 || d > levels || i < 0 || i >= (1 << d)) return PDWT_EINVAL;
-        const int span = 1 << (levels - d);
-        for (int j = i * span; j < (i + 1) * span; j++) {
-            if (leaf[j]) return PDWT_EINVAL;  // two nodes on one root-to-leaf path
-            leaf[j] = 1;
-        }
-        out[((1 << d) - 1) + i] = WP1_LOAD;
-    }
-    for (size_t j = 0; j < leaf.size(); j++)
-        if (!leaf[j]) return PDWT_EINVAL;  // a path that meets no node
-    for (int l = levels - 1; l >= 0; l--)
-        for (int i = 0; i < (1 << l); i++) {
-            const unsigned char* kid = out + ((2 << l) - 1) + 2 * i;
-            if (kid[0] != WP1_SKIP || kid[1] != WP1_SKIP) out[((1 << l) - 1) + i] = WP1_SYNTH;
-        }
-    out[total] = 0;  // (the table is 2^(levels + 1) bytes)
-    return PDWT_OK;
+    const int rc = packet_state_table<2>(levels, kWp1MaxLev, depth, idx, n, out);
+    if (rc == PDWT_OK) out[(2 << levels) - 1] = 0;  // (the table is 2^(levels + 1) bytes)
+    return rc;
 }
 int pdwt_memcpy2d(void* dst, size_t dpitch, const void* src, size_t spitch, size_t width, size_t height, int kind)
 {

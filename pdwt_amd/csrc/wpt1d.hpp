@@ -20,6 +20,8 @@
 //   inverse  [c' cells | n_l coefficients | h2 - 1 - c' + shift cells], segment stride wp1_iseg = n_l + h2; the window of pair q starts at cell q
 // The halos are written by a full modulo (F - 2 can exceed n_l), so the item loops have no index map and no branch.
 #pragma once
+#include <vector>
+
 #include "dwt_ext1d.hpp"
 
 namespace pdwt {
@@ -61,6 +63,50 @@ __host__ __device__ inline int wp1_wrap_per(int s, int n)
         if (s < 0) s += n;
     }
     return s;
+}
+
+// ---- host: what the packet families (wpt1d.hip, wpt2db.hip) ask of a bank, a size and a basis -------------------------------------------
+inline bool packet_bank_ok(int hlen) { return hlen >= 2 && hlen <= PDWT_MAX_FILTER_WIDTH && !(hlen & 1); }
+inline int packet_ilog2(int v)
+{
+    int l = 0;
+    while (v > 1) v >>= 1, l++;
+    return l;
+}
+
+// The node-state table of a basis given as n (depth, index) pairs of a tree of `levels` depths with ARITY (2 or 4) children per node:
+// one byte per node, node i of depth l at (ARITY^l - 1) / (ARITY - 1) + i; LOAD for a basis node, SYNTH for every node above one, SKIP
+// below.  PDWT_EINVAL unless every root-to-leaf path meets exactly one node of the basis.
+template <int ARITY>
+inline int packet_state_table(int levels, int max_levels, const int* depth, const int* idx, int n, unsigned char* out)
+{
+    static_assert(ARITY == 2 || ARITY == 4, "binary trees of rows, quad-trees of images");
+    constexpr int B = ARITY == 4 ? 2 : 1;  // nodes of depth l: 1 << (B * l)
+    auto nodes = [](int l) { return 1 << (B * l); };
+    auto off = [&](int l) { return (nodes(l) - 1) / (ARITY - 1); };
+    if (levels < 1 || levels > max_levels || !depth || !idx || !out || n < 1) return PDWT_EINVAL;
+    const int total = off(levels + 1);
+    std::vector<unsigned char> leaf((size_t)nodes(levels), 0);
+    for (int k = 0; k < total; k++) out[k] = WP1_SKIP;
+    for (int k = 0; k < n; k++) {
+        const int d = depth[k], i = idx[k];
+        if (d < 0 || d > levels || i < 0 || i >= nodes(d)) return PDWT_EINVAL;
+        const int span = nodes(levels - d);
+        for (int j = i * span; j < (i + 1) * span; j++) {
+            if (leaf[j]) return PDWT_EINVAL;  // two nodes on one root-to-leaf path
+            leaf[j] = 1;
+        }
+        out[off(d) + i] = WP1_LOAD;
+    }
+    for (size_t j = 0; j < leaf.size(); j++)
+        if (!leaf[j]) return PDWT_EINVAL;  // a path that meets no node
+    for (int l = levels - 1; l >= 0; l--)
+        for (int i = 0; i < nodes(l); i++) {
+            const unsigned char* kid = out + off(l + 1) + ARITY * i;
+            for (int q = 0; q < ARITY; q++)
+                if (kid[q] != WP1_SKIP) out[off(l) + i] = WP1_SYNTH;
+        }
+    return PDWT_OK;
 }
 
 // ---- the only places where taps meet samples ------------------------------------------------------------------------------------

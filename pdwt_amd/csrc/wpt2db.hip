@@ -13,7 +13,7 @@
 //   per depth             images that do not fit LDS, and allow_fused = 0: the level entries of wpt2d.hip on the forest, in chunks of at
 //                         most 16384 parents (no kernel of its own).  4^l divides 16384, so a chunk is a whole number of images and the
 //                         chunk-relative parent list of a partial basis is the SAME for every chunk (the last one takes a prefix).
-// The stages of the fused kernels are the functions of wpt2db.hpp; all forms (and a loop over WaveletPackets instances) compute the same
+// The pipelines of the fused kernels are the functions of wpt2db.hpp, their stages those of image_stages.hpp; all forms (and a loop over WaveletPackets instances) compute the same
 // bits.  Barriers between LDS stages are LDS-only (lgkmcnt), so the child stores of a depth are not waited for.
 //
 // Workgroup size 512, for the reason given in dwt_ext2db.hip: an image above 80 KiB has the compute unit to itself and needs two waves per
@@ -23,7 +23,6 @@
 //   tab = ru4(2 max(nr_1, nc_1) + hlen - 2) ints     st  = ru16(sum_{l <= L} 4^l) bytes
 //   forward (cur + tmp) elem + 8 tab;  inverse the same + st.  Fused when the larger fits 160 KiB.
 #include <algorithm>
-#include <vector>
 
 #include "wpt2db.hpp"
 
@@ -33,10 +32,6 @@ constexpr int kWpbMaxBatch = 65535;
 constexpr long long kWpbMaxForest = 1ll << 22;  // B 4^L: bounds the pointer and state tables of the class
 constexpr int kWpbChunk = 16384;                // parents per launch of a level entry of wpt2d.hip
 
-struct WpbLdsBarrier {
-    __device__ __forceinline__ void operator()() const { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
-};
-
 template <typename T, int HL>
 __global__ __launch_bounds__(kWpbThreads) void k_wpb_fwd_fused(const T* __restrict__ src, WpbTree<T> t, WpbLds lds, Taps2<T> taps)
 {
@@ -44,7 +39,7 @@ __global__ __launch_bounds__(kWpbThreads) void k_wpb_fwd_fused(const T* __restri
     T* cur = reinterpret_cast<T*>(smem);
     T* tmp = cur + lds.cur;
     int* cmap = reinterpret_cast<int*>(tmp + lds.tmp);
-    wpb_fwd_image<T, HL, kWpbThreads>(cur, tmp, cmap, cmap + lds.tab, src, t, (size_t)blockIdx.x, taps, (int)threadIdx.x, WpbLdsBarrier());
+    wpb_fwd_image<T, HL, kWpbThreads>(cur, tmp, cmap, cmap + lds.tab, src, t, (size_t)blockIdx.x, taps, (int)threadIdx.x, LdsBarrier());
 }
 
 template <typename T, int HL>
@@ -55,7 +50,7 @@ __global__ __launch_bounds__(kWpbThreads) void k_wpb_inv_fused(T* __restrict__ d
     T* tmp = cur + lds.cur;
     int* cmap = reinterpret_cast<int*>(tmp + lds.tmp);
     unsigned char* stl = reinterpret_cast<unsigned char*>(cmap + 2 * lds.tab);
-    wpb_inv_image<T, HL, kWpbThreads>(cur, tmp, cmap, cmap + lds.tab, stl, state, dst, t, (size_t)blockIdx.x, taps, (int)threadIdx.x, WpbLdsBarrier());
+    wpb_inv_image<T, HL, kWpbThreads>(cur, tmp, cmap, cmap + lds.tab, stl, state, dst, t, (size_t)blockIdx.x, taps, (int)threadIdx.x, LdsBarrier());
 }
 
 template <typename T>
@@ -63,7 +58,7 @@ __global__ __launch_bounds__(kWpbThreads) void k_wpb_haar_fwd_fused(const T* __r
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     T* b0 = reinterpret_cast<T*>(smem);
-    wpb_haar_fwd_image<T, kWpbThreads>(b0, b0 + lds.cur, src, t, (size_t)blockIdx.x, (int)threadIdx.x, WpbLdsBarrier());
+    wpb_haar_fwd_image<T, kWpbThreads>(b0, b0 + lds.cur, src, t, (size_t)blockIdx.x, (int)threadIdx.x, LdsBarrier());
 }
 
 template <typename T>
@@ -72,23 +67,16 @@ __global__ __launch_bounds__(kWpbThreads) void k_wpb_haar_inv_fused(T* __restric
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     T* b0 = reinterpret_cast<T*>(smem);
     unsigned char* stl = reinterpret_cast<unsigned char*>(reinterpret_cast<int*>(b0 + lds.cur + lds.tmp) + 2 * lds.tab);
-    wpb_haar_inv_image<T, kWpbThreads>(b0, b0 + lds.cur, stl, state, dst, t, (size_t)blockIdx.x, (int)threadIdx.x, WpbLdsBarrier());
+    wpb_haar_inv_image<T, kWpbThreads>(b0, b0 + lds.cur, stl, state, dst, t, (size_t)blockIdx.x, (int)threadIdx.x, LdsBarrier());
 }
 
 // ---- geometry (host, no device; the plan is wpb_plan of wpt2db.hpp) -------------------------------------------------------------------
-static bool wpb_bank_ok(int hlen) { return hlen >= 2 && hlen <= PDWT_MAX_FILTER_WIDTH && !(hlen & 1); }
-static int wpb_ilog2(int v)
-{
-    int l = 0;
-    while (v > 1) v >>= 1, l++;
-    return l;
-}
 // WaveletPackets::geometry: the clamped depth (0: too small, a bad size or a bad bank) and the node shapes of depth 0 .. that depth
 static int wpb_geometry(int Nr, int Nc, int hlen, int levels, int* nr, int* nc)
 {
-    if (Nr < 1 || Nc < 1 || !wpb_bank_ok(hlen) || (unsigned long long)Nr * (unsigned long long)Nc >= (1ull << 31)) return 0;
+    if (Nr < 1 || Nc < 1 || !packet_bank_ok(hlen) || (unsigned long long)Nr * (unsigned long long)Nc >= (1ull << 31)) return 0;
     if (levels < 1) levels = 1;
-    int lmax = wpb_ilog2((Nr < Nc ? Nr : Nc) / (hlen - 1));
+    int lmax = packet_ilog2((Nr < Nc ? Nr : Nc) / (hlen - 1));
     if (lmax > kWpbMaxLev) lmax = kWpbMaxLev;
     if (levels > lmax) levels = lmax;
     for (int l = 0; l <= levels; l++) {
@@ -118,33 +106,6 @@ static bool wpb_fill_tree(WpbTree<T>& t, T* const* nodes, int Nr, int Nc, int L)
         t.p[l] = nodes[l - 1], t.nr[l] = div2(t.nr[l - 1]), t.nc[l] = div2(t.nc[l - 1]);
     }
     return true;
-}
-
-// the state table of a basis: pdwt_wp1_state_table with four children per node
-static int wpb_state_table(int levels, const int* depth, const int* idx, int n, unsigned char* out)
-{
-    if (levels < 1 || levels > kWpbMaxLev || !depth || !idx || !out || n < 1) return PDWT_EINVAL;
-    const int total = wpb_state_off(levels + 1);
-    std::vector<unsigned char> leaf((size_t)wpb_nodes(levels), 0);
-    for (int k = 0; k < total; k++) out[k] = WPB_SKIP;
-    for (int k = 0; k < n; k++) {
-        const int d = depth[k], i = idx[k];
-        if (d < 0 || d > levels || i < 0 || i >= wpb_nodes(d)) return PDWT_EINVAL;
-        const int span = wpb_nodes(levels - d);
-        for (int j = i * span; j < (i + 1) * span; j++) {
-            if (leaf[j]) return PDWT_EINVAL;  // two nodes on one root-to-leaf path
-            leaf[j] = 1;
-        }
-        out[wpb_state_off(d) + i] = WPB_LOAD;
-    }
-    for (size_t j = 0; j < leaf.size(); j++)
-        if (!leaf[j]) return PDWT_EINVAL;  // a path that meets no node
-    for (int l = levels - 1; l >= 0; l--)
-        for (int i = 0; i < wpb_nodes(l); i++) {
-            const unsigned char* kid = out + wpb_state_off(l + 1) + 4 * i;
-            if (kid[0] != WPB_SKIP || kid[1] != WPB_SKIP || kid[2] != WPB_SKIP || kid[3] != WPB_SKIP) out[wpb_state_off(l) + i] = WPB_SYNTH;
-        }
-    return PDWT_OK;
 }
 
 // Is the table one a state_table call can have written?  (The kernels index LDS by it: checked before every inverse.)
@@ -205,24 +166,18 @@ template <> struct WpbLevelFn<double> {
 template <typename T, int HL>
 static int launch_wpb_fwd(const T* src, const WpbTree<T>& t, int B, const WpbPlan& p, const Taps2<T>& taps)
 {
-    const void* kfn = HL == 2 ? (const void*)k_wpb_haar_fwd_fused<T> : (const void*)k_wpb_fwd_fused<T, (HL == 2 ? 4 : HL)>;
-    if (p.lds_fwd > 64 * 1024)
-        if (const int rc = lds_opt_in_ptr(kfn); rc != PDWT_OK) return rc;
-    if constexpr (HL == 2) hipLaunchKernelGGL((k_wpb_haar_fwd_fused<T>), dim3(B), dim3(kWpbThreads), p.lds_fwd, stream(), src, t, p.lds);
-    else hipLaunchKernelGGL((k_wpb_fwd_fused<T, HL>), dim3(B), dim3(kWpbThreads), p.lds_fwd, stream(), src, t, p.lds, taps);
-    PDWT_HIP_TRY(hipGetLastError());
-    return PDWT_WPTB_FUSED;
+    int rc;
+    if constexpr (HL == 2) rc = launch_lds(k_wpb_haar_fwd_fused<T>, dim3(B), dim3(kWpbThreads), p.lds_fwd, src, t, p.lds);
+    else rc = launch_lds(k_wpb_fwd_fused<T, HL>, dim3(B), dim3(kWpbThreads), p.lds_fwd, src, t, p.lds, taps);
+    return rc == PDWT_OK ? PDWT_WPTB_FUSED : rc;
 }
 template <typename T, int HL>
 static int launch_wpb_inv(T* dst, const WpbTree<T>& t, const unsigned char* d_state, int B, const WpbPlan& p, const Taps2<T>& taps)
 {
-    const void* kfn = HL == 2 ? (const void*)k_wpb_haar_inv_fused<T> : (const void*)k_wpb_inv_fused<T, (HL == 2 ? 4 : HL)>;
-    if (p.lds_inv > 64 * 1024)
-        if (const int rc = lds_opt_in_ptr(kfn); rc != PDWT_OK) return rc;
-    if constexpr (HL == 2) hipLaunchKernelGGL((k_wpb_haar_inv_fused<T>), dim3(B), dim3(kWpbThreads), p.lds_inv, stream(), dst, t, d_state, p.lds);
-    else hipLaunchKernelGGL((k_wpb_inv_fused<T, HL>), dim3(B), dim3(kWpbThreads), p.lds_inv, stream(), dst, t, d_state, p.lds, taps);
-    PDWT_HIP_TRY(hipGetLastError());
-    return PDWT_WPTB_FUSED;
+    int rc;
+    if constexpr (HL == 2) rc = launch_lds(k_wpb_haar_inv_fused<T>, dim3(B), dim3(kWpbThreads), p.lds_inv, dst, t, d_state, p.lds);
+    else rc = launch_lds(k_wpb_inv_fused<T, HL>, dim3(B), dim3(kWpbThreads), p.lds_inv, dst, t, d_state, p.lds, taps);
+    return rc == PDWT_OK ? PDWT_WPTB_FUSED : rc;
 }
 
 template <typename T>
@@ -311,7 +266,7 @@ long long pdwt_wptb_tmp_elems(int B, int Nr, int Nc, int hlen, int levels, int e
     if (fu < 0 || !wpb_ok(B, Nr, Nc, hlen, L)) return PDWT_EINVAL;
     return fu && allow_fused ? 0 : wpb_list_off(B, L);
 }
-int pdwt_wptb_state_table(int levels, const int* depth, const int* idx, int n, unsigned char* out) { return wpb_state_table(levels, depth, idx, n, out); }
+int pdwt_wptb_state_table(int levels, const int* depth, const int* idx, int n, unsigned char* out) { return packet_state_table<4>(levels, kWpbMaxLev, depth, idx, n, out); }
 long long pdwt_wptb_chunk_lists(int B, int levels, const unsigned char* state, int* lists)
 {
     if (B < 1 || B > kWpbMaxBatch || levels < 1 || levels > kWpbMaxLev || !state || (long long)B * wpb_nodes(levels) > kWpbMaxForest || !wpb_state_valid(levels, state))

@@ -1,7 +1,8 @@
-// wpt2db.hpp -- the stages of the fused kernels of the batched 2-D wavelet packet transform (wpt2db.hip; include/pdwt_hip.h "Batched 2-D
-// wavelet packets"): the whole quad-tree of ONE image in the LDS of one workgroup.  As in wpt1d.hpp and dwt_ext2db.hpp every stage takes
-// the thread count as a template argument and the thread index as an argument and contains no barrier; the pipelines (wpb_*_image) take
-// the barrier as a functor.  The kernels pass the LDS-only barrier and NT = 512; a host program passes a no-op and NT = 1, tid = 0 and
+// wpt2db.hpp -- the pipelines of the fused kernels of the batched 2-D wavelet packet transform (wpt2db.hip; include/pdwt_hip.h "Batched
+// 2-D wavelet packets"): the whole quad-tree of ONE image in the LDS of one workgroup.  The stages are those of image_stages.hpp, shared
+// with the inverse of the boundary modes (dwt_ext2db.hpp), run on the periodised line: window offset -(F/2 - 1), 2 * 4^l line pairs per
+// pass, a synthesis with shift, centre and table under an optional state table.  Every stage takes the thread count as a template
+// argument and the thread index as an argument and contains no barrier; the pipelines (wpb_*_image) take the barrier as a functor.  The kernels pass the LDS-only barrier and NT = 512; a host program passes a no-op and NT = 1, tid = 0 and
 // runs whole pipelines on the CPU under a sanitizer.
 //
 // Values.  The operation sequence is that of k_wp_fwd / k_wp_inv (wpt2d.hip), so the results are the same bits: forward rows first with
@@ -20,8 +21,7 @@
 #pragma once
 #include <algorithm>
 
-#include "dwt_ext2db.hpp"
-#include "wpt1d.hpp"
+#include "image_stages.hpp"
 
 namespace pdwt {
 
@@ -30,6 +30,8 @@ constexpr int kWpbMaxLev = 7;  // WPT_MAX_LEVELS
 
 // node states of the inverse (one byte per node, node i of depth l at (4^l - 1) / 3 + i) and what a depth holds of one of them
 enum WpbState : unsigned char { WPB_SKIP = 0, WPB_LOAD = 1, WPB_SYNTH = 2 };
+static_assert((int)WPB_SKIP == (int)WP1_SKIP && (int)WPB_LOAD == (int)WP1_LOAD && (int)WPB_SYNTH == (int)WP1_SYNTH && WPB_SYNTH == kImgSynth,
+              "one table format: packet_state_table (wpt1d.hpp) writes it, the stages of image_stages.hpp read it");
 enum WpbSummary : unsigned char { WPB_NONE = 0, WPB_ALL = 1, WPB_MIXED = 2 };
 
 template <typename T>
@@ -44,8 +46,6 @@ __host__ __device__ inline int wpb_nodes(int l) { return 1 << (2 * l); }
 __host__ __device__ inline int wpb_state_off(int l) { return (wpb_nodes(l) - 1) / 3; }
 
 // ---- the plan (host, no device): the single source of the decision and of the LDS bytes of both launches ----------------------------------
-constexpr size_t kWpbLdsMax = 160 * 1024;  // the hard ceiling of a workgroup
-
 struct WpbLds {
     int cur, tmp, tab;  // elements, elements, ints
 };
@@ -70,7 +70,7 @@ inline WpbPlan wpb_plan(int Nr, int Nc, int hlen, int L, size_t elem)
     WpbPlan p;
     p.lds_fwd = (cur + tmp) * elem + 2 * tab * sizeof(int);
     p.lds_inv = p.lds_fwd + st;
-    p.fused = std::max(p.lds_fwd, p.lds_inv) <= kWpbLdsMax;
+    p.fused = std::max(p.lds_fwd, p.lds_inv) <= kLdsMax;
     p.lds.cur = p.fused ? (int)cur : 0, p.lds.tmp = p.fused ? (int)tmp : 0, p.lds.tab = (int)tab;
     return p;
 }
@@ -80,63 +80,25 @@ inline WpbPlan wpb_plan(int Nr, int Nc, int hlen, int L, size_t elem)
 template <int NT>
 __host__ __device__ __forceinline__ void wpb_fill_fmap(int* map, int n, int half, int F, int tid)
 {
-    const int cnt = 2 * half + F - 2, c = F / 2 - 1;
-    for (int k = tid; k < cnt; k += NT) map[k] = wp1_wrap_ext(k - c, n);
+    img_fill_map<NT>(map, 2 * half + F - 2, [&](int k) { return wp1_wrap_ext(k - (F / 2 - 1), n); }, tid);
 }
 
-// Analysis along the `rows` rows (of all nodes of a depth) of cur[rows][nc]: low pass into tmp[0][rows][hc], high pass into tmp[1][rows][hc]
-template <typename T, int HL, int NT>
-__host__ __device__ __forceinline__ void wpb_rows_analysis(const T* cur, T* tmp, const int* cmap, int rows, int nc, int hc, const Taps2<T>& taps, int tid)
-{
-    constexpr int c = HL / 2 - 1;
-    const int total = rows * hc;
-    for (int e = tid; e < total; e += NT) {
-        const int r = e / hc, ox = e - r * hc;
-        const T* row = cur + r * nc;
-        const int s0 = 2 * ox - c;
-        T lo, hi;
-        if (s0 >= 0 && s0 + HL <= nc) {
-            const T* p = row + s0;
-            ext2db_fwd_item<T, HL>([&](int j) { return p[j]; }, taps, lo, hi);
-        } else {
-            const int* m = cmap + 2 * ox;
-            ext2db_fwd_item<T, HL>([&](int j) { return row[m[j]]; }, taps, lo, hi);
-        }
-        tmp[e] = lo;
-        tmp[total + e] = hi;
-    }
-}
-
-// Analysis along the columns of tmp[2][nodes * nr][hc]: row low -> A (column low), H (column high); row high -> V, D.  Work items are
-// numbered across (node, row band, row, position), position fastest: lanes write contiguous runs of a child node.  The children go to the
-// image's depth-(l+1) line at g and, nxt != NULL, to the same offsets of nxt.
+// The column pass of a depth: lanes write contiguous runs of a child node (4k + 2xb, and its neighbour), to the image's depth-(l+1) line
+// at g and, nxt != NULL, to the same offsets of nxt.  (g is a parameter so that it can be __restrict__ for the whole pass.)
 template <typename T, int HL, int NT>
 __host__ __device__ __forceinline__ void wpb_cols_analysis(const T* tmp, const int* rmap, T* nxt, T* __restrict__ g, int nodes, int nr, int hr, int hc, const Taps2<T>& taps,
                                                            int tid)
 {
-    constexpr int c = HL / 2 - 1;
-    const int per = hr * hc, plane = nodes * nr * hc, total = 2 * nodes * per;
-    for (int e = tid; e < total; e += NT) {
-        const int kb = e / per, o = e - kb * per, k = kb >> 1, xb = kb & 1;
-        const int oy = o / hc, ox = o - oy * hc;
-        const T* col = tmp + xb * plane + k * nr * hc + ox;
-        const int s0 = 2 * oy - c;
-        T lo, hi;
-        if (s0 >= 0 && s0 + HL <= nr) {
-            const T* p = col + s0 * hc;
-            ext2db_fwd_item<T, HL>([&](int j) { return p[j * hc]; }, taps, lo, hi);
-        } else {
-            const int* m = rmap + 2 * oy;
-            ext2db_fwd_item<T, HL>([&](int j) { return col[m[j] * hc]; }, taps, lo, hi);
-        }
-        const int off = (2 * kb) * per + o;  // child 4k + 2xb
+    const int per = hr * hc;
+    img_cols_analysis<T, HL, -(HL / 2 - 1), NT>(tmp, rmap, 2 * nodes, nr, hr, hc, taps, tid, [&](int kb, int o, T lo, T hi) {
+        const int off = (2 * kb) * per + o;
         g[off] = lo;
         g[off + per] = hi;
         if (nxt) {
             nxt[off] = lo;
             nxt[off + per] = hi;
         }
-    }
+    });
 }
 
 // All depths of image `ib`.  cur: cur_elems of the plan, tmp likewise, cmap / rmap: `tab` ints each.
@@ -145,13 +107,13 @@ __host__ __device__ __forceinline__ void wpb_fwd_image(T* cur, T* tmp, int* cmap
                                                        int tid, Bar bar)
 {
     const int L = t.L;
-    ext2db_copy_in<T, NT>(cur, src + ib * ((size_t)t.nr[0] * t.nc[0]), t.nr[0] * t.nc[0], tid);
+    img_copy_in<T, NT>(cur, src + ib * ((size_t)t.nr[0] * t.nc[0]), t.nr[0] * t.nc[0], tid);
     wpb_fill_fmap<NT>(cmap, t.nc[0], t.nc[1], HL, tid);
     bar();
     for (int l = 0; l < L; l++) {
         const int nodes = wpb_nodes(l), nr = t.nr[l], nc = t.nc[l], hr = t.nr[l + 1], hc = t.nc[l + 1];
         wpb_fill_fmap<NT>(rmap, nr, hr, HL, tid);  // (read by the column pass, after the barrier; the last one was read before the previous)
-        wpb_rows_analysis<T, HL, NT>(cur, tmp, cmap, nodes * nr, nc, hc, taps, tid);
+        img_rows_analysis<T, HL, -(HL / 2 - 1), NT>(cur, tmp, cmap, nodes * nr, nc, hc, taps, tid);
         bar();
         const bool last = l + 1 == L;
         T* g = t.p[l + 1] + ib * ((size_t)(4 * nodes) * hr * hc);
@@ -167,7 +129,7 @@ template <typename T, int NT, typename Bar>
 __host__ __device__ __forceinline__ void wpb_haar_fwd_image(T* b0, T* b1, const T* __restrict__ src, const WpbTree<T>& t, size_t ib, int tid, Bar bar)
 {
     const int L = t.L;
-    ext2db_copy_in<T, NT>(b0, src + ib * ((size_t)t.nr[0] * t.nc[0]), t.nr[0] * t.nc[0], tid);
+    img_copy_in<T, NT>(b0, src + ib * ((size_t)t.nr[0] * t.nc[0]), t.nr[0] * t.nc[0], tid);
     bar();
     T *cur = b0, *nxt = b1;
     for (int l = 0; l < L; l++) {
@@ -199,31 +161,7 @@ __host__ __device__ __forceinline__ void wpb_haar_fwd_image(T* b0, T* b1, const 
 template <int NT>
 __host__ __device__ __forceinline__ void wpb_fill_imap(int* map, int n, int N, int F, int tid)
 {
-    const int cnt = wp1_pairs(n, F) + F / 2 - 1, c = F / 4;
-    for (int k = tid; k < cnt; k += NT) map[k] = wp1_wrap_per(k - c, N);
-}
-
-// (x0, x1) = the samples 2q - shift, 2q - shift + 1 of a line from the coefficients ga(m), gd(m), m = 0 .. HL/2 - 1: ext2db_inv_item with getters
-template <typename T, int HL, typename GetA, typename GetD>
-__host__ __device__ __forceinline__ void wpb_inv_item(GetA ga, GetD gd, const Taps2<T>& taps, T& x0, T& x1)
-{
-    const int z0 = ext2db_opaque_taps<T, HL>() ? ext1d_zero() : 0;
-    T ae = T(0), ao = T(0), de = T(0), dd = T(0);
-    auto step = [&](int m) {
-        const T ca = ga(m), cd = gd(m);
-        ae = ext1d_fma(ca, taps.a[HL - 2 - 2 * m + z0], ae);
-        ao = ext1d_fma(ca, taps.a[HL - 1 - 2 * m + z0], ao);
-        de = ext1d_fma(cd, taps.b[HL - 2 - 2 * m + z0], de);
-        dd = ext1d_fma(cd, taps.b[HL - 1 - 2 * m + z0], dd);
-    };
-    if constexpr (ext2db_opaque_taps<T, HL>()) {
-#pragma unroll 4
-        for (int m = 0; m < HL / 2; m++) step(m);
-    } else {
-#pragma unroll
-        for (int m = 0; m < HL / 2; m++) step(m);
-    }
-    x0 = ae + de, x1 = ao + dd;
+    img_fill_map<NT>(map, wp1_pairs(n, F) + F / 2 - 1, [&](int k) { return wp1_wrap_per(k - F / 4, N); }, tid);
 }
 
 // Stage the LOAD nodes of a depth (`nodes` of `per` elements, the image's line at g) into buf at their own offsets
@@ -231,68 +169,11 @@ template <typename T, int NT>
 __host__ __device__ __forceinline__ void wpb_stage_nodes(T* buf, const T* __restrict__ g, const unsigned char* st, int summary, int nodes, int per, int tid)
 {
     if (summary == WPB_ALL) {
-        ext2db_copy_in<T, NT>(buf, g, nodes * per, tid);
+        img_copy_in<T, NT>(buf, g, nodes * per, tid);
     } else if (summary == WPB_MIXED) {
         const int total = nodes * per;
         for (int e = tid; e < total; e += NT)
             if (st[e / per] == WPB_LOAD) buf[e] = g[e];
-    }
-}
-
-// Synthesis along the columns of the children of every SYNTH parent (st == NULL: of every parent): ch holds depth l + 1 (4 * nodes nodes of
-// hr x hc), cb receives [nodes][2][nr][hc], (A, H) -> plane 0, (V, D) -> plane 1 of the parent.  Two rows per work item.
-template <typename T, int HL, int NT>
-__host__ __device__ __forceinline__ void wpb_cols_synthesis(const T* ch, T* cb, const int* rmap, const unsigned char* st, int nodes, int nr, int hr, int hc,
-                                                            const Taps2<T>& taps, int tid)
-{
-    constexpr int h2 = HL / 2, cq = HL / 4;
-    const int sh = wp1_shift(HL), Q = wp1_pairs(nr, HL), per = Q * hc, total = 2 * nodes * per;
-    for (int e = tid; e < total; e += NT) {
-        const int kb = e / per, rem = e - kb * per, k = kb >> 1;
-        if (st && st[k] != WPB_SYNTH) continue;
-        const int q = rem / hc, cc = rem - q * hc;
-        const T* a = ch + (2 * kb) * hr * hc + cc;  // child 4k + 2xb, and its neighbour
-        const T* d = a + hr * hc;
-        T x0, x1;
-        if (q - cq >= 0 && q - cq + h2 <= hr) {
-            const T *pa = a + (q - cq) * hc, *pd = d + (q - cq) * hc;
-            wpb_inv_item<T, HL>([&](int m) { return pa[m * hc]; }, [&](int m) { return pd[m * hc]; }, taps, x0, x1);
-        } else {
-            const int* mp = rmap + q;
-            wpb_inv_item<T, HL>([&](int m) { return a[mp[m] * hc]; }, [&](int m) { return d[mp[m] * hc]; }, taps, x0, x1);
-        }
-        const int g0 = 2 * q - sh;
-        T* o = cb + kb * nr * hc + cc;
-        if (g0 >= 0) o[g0 * hc] = x0;
-        if (g0 + 1 < nr) o[(g0 + 1) * hc] = x1;
-    }
-}
-
-// Synthesis along the rows of cb into the parents: out + k * nr * nc is parent k (LDS, or the image in HBM).  Two samples per work item.
-template <typename T, int HL, int NT>
-__host__ __device__ __forceinline__ void wpb_rows_synthesis(const T* cb, T* out, const int* cmap, const unsigned char* st, int nodes, int nr, int nc, int hc,
-                                                            const Taps2<T>& taps, int tid)
-{
-    constexpr int h2 = HL / 2, cq = HL / 4;
-    const int sh = wp1_shift(HL), Q = wp1_pairs(nc, HL), per = nr * Q, total = nodes * per;
-    for (int e = tid; e < total; e += NT) {
-        const int k = e / per, rem = e - k * per;
-        if (st && st[k] != WPB_SYNTH) continue;
-        const int r = rem / Q, q = rem - r * Q;
-        const T* a = cb + ((2 * k) * nr + r) * hc;
-        const T* d = a + nr * hc;
-        T x0, x1;
-        if (q - cq >= 0 && q - cq + h2 <= hc) {
-            const T *pa = a + (q - cq), *pd = d + (q - cq);
-            wpb_inv_item<T, HL>([&](int m) { return pa[m]; }, [&](int m) { return pd[m]; }, taps, x0, x1);
-        } else {
-            const int* mp = cmap + q;
-            wpb_inv_item<T, HL>([&](int m) { return a[mp[m]]; }, [&](int m) { return d[mp[m]]; }, taps, x0, x1);
-        }
-        const int g0 = 2 * q - sh;
-        T* o = out + (size_t)k * nr * nc + (size_t)r * nc;
-        if (g0 >= 0) o[g0] = x0;
-        if (g0 + 1 < nc) o[g0 + 1] = x1;
     }
 }
 
@@ -327,13 +208,14 @@ __host__ __device__ __forceinline__ void wpb_inv_image(T* cur, T* tmp, int* cmap
         const unsigned char* sl = t.synth[l] == WPB_MIXED ? st + wpb_state_off(l) : nullptr;
         const bool any = t.synth[l] != WPB_NONE;
         wpb_fill_imap<NT>(cmap, nc, hc, HL, tid);  // (its last reader, the row synthesis of the depth below, is behind a barrier)
-        if (any) wpb_cols_synthesis<T, HL, NT>(cur, tmp, rmap, sl, nodes, nr, hr, hc, taps, tid);
+        // the children of every SYNTH parent: cur holds depth l + 1 (4 * nodes nodes of hr x hc); tmp receives [nodes][2][nr][hc]
+        if (any) img_cols_synthesis<T, HL, true, 0, NT>(cur, cur + hr * hc, 2 * hr * hc, tmp, rmap, sl, 2 * nodes, nr, hr, hc, taps, tid);
         bar();
         if (l == 0) {
-            if (any) wpb_rows_synthesis<T, HL, NT>(tmp, dst + ib * ((size_t)nr * nc), cmap, sl, 1, nr, nc, hc, taps, tid);
+            if (any) img_rows_synthesis<T, HL, true, 0, NT>(tmp, dst + ib * ((size_t)nr * nc), cmap, sl, 1, nr, nc, hc, taps, tid);
             break;
         }
-        if (any) wpb_rows_synthesis<T, HL, NT>(tmp, cur, cmap, sl, nodes, nr, nc, hc, taps, tid);
+        if (any) img_rows_synthesis<T, HL, true, 0, NT>(tmp, cur, cmap, sl, nodes, nr, nc, hc, taps, tid);
         wpb_stage_nodes<T, NT>(cur, t.p[l] + ib * ((size_t)nodes * nr * nc), st + (st ? wpb_state_off(l) : 0), t.load[l], nodes, nr * nc, tid);
         wpb_fill_imap<NT>(rmap, t.nr[l - 1], nr, HL, tid);
         bar();
