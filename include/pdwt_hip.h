@@ -697,6 +697,46 @@ int pdwt_ext3d_inverse_adjoint_level_f32(const float* d_src, float* const* d_ban
 int pdwt_ext3d_inverse_adjoint_level_f64(const double* d_src, double* const* d_bands, int nz, int nr, int nc, const pdwt_filters_f64* f, double* d_tmp);
 
 /* ---------------------------------------------------------------------------------------------
+ * Batched 3-D DWT with boundary modes (pdwt_amd/csrc/dwt_ext3db.hip): the transform of the two sections above, W, its inverse S and
+ * the adjoints W^T and S^T, on a contiguous stack of V volumes of Nz x Nr x Nc (volume-major), ALL `levels` levels in one call.  Volume
+ * v of every result holds, bit for bit, what the chain of level entries above (pdwt_ext3d_forward_level_*, _inverse_level_*,
+ * _forward_adjoint_level_*, _inverse_adjoint_level_*) gives on volume v alone, in every mode and either precision: the x-y passes are
+ * the level entries' own launches on the V * nz planes of the stack (chunks of at most 65535 planes), the z passes put the (volume,
+ * quadrant) pairs on the grid (chunks of at most 65535 pairs).  No atomics; nothing synchronises with the host between levels or
+ * chunks: a call is asynchronous on the library stream.
+ *
+ * d_bands is a HOST table of 7 * levels + 1 device pointers in the order of pdwt_ext3d_band_shape: [A_L, the 7 details of level L,
+ * ..., the 7 details of level 1], a level's details in the order aad, ada, add, daa, dad, dda, ddd.  Band k is ONE contiguous stack
+ * V x nz_l x nr_l x nc_l (n_l = (n_{l-1} + F - 1) / 2, n_0 = N, F = f->hlen).  forward reads d_src and writes the bands; inverse reads
+ * the bands and writes d_dst; forward_adjoint reads the cotangent bands and writes d_dst; inverse_adjoint (the forward in mode 0 with
+ * the bank IL, IH reversed) reads d_src and writes the bands.  forward and inverse_adjoint leave d_src intact, inverse and
+ * forward_adjoint leave the bands intact.  d_src / d_dst must not overlap a band or d_tmp.  Levels are NOT clamped: 1 .. 13.
+ *
+ * Scratch, in elements (pdwt_ext3db_tmp_elems for forward, inverse and inverse_adjoint; pdwt_ext3db_adjoint_tmp_elems for
+ * forward_adjoint, which is never smaller and serves all four); contents afterwards are unspecified:
+ *   tmp_elems         = 4 * V * Nz * nr_1 * nc_1                          the four x-y quadrant stacks of level 1
+ *                     + (levels > 1 ? 2 * V * nz_1 * nr_1 * nc_1 : 0)     two approximation (cotangent) stacks, used in turn
+ *   adjoint_tmp_elems = tmp_elems + max over l = 0 .. levels - 1 of V * nz_l * ((2 nr_{l+1} + F - 2) * (2 nc_{l+1} + F - 2) - nr_l * nc_l)
+ *                                                                         the frames of the planes of the 2-D level adjoint
+ *
+ * PDWT_EINVAL (tmp_elems: PDWT_EINVAL too), before anything is launched or touched: a NULL pointer or a NULL entry of the table;
+ * V < 1; mode outside 0 .. 4; levels outside 1 .. 13; a level whose nz_l x nr_l x nc_l volume the level entries refuse (an axis
+ * shorter than F - 1, nz_l > 65535, ...); for the two adjoints also what the 2-D level adjoint refuses on a chunk of min(V * nz_l,
+ * 65535) planes; and a stack of V * Nz >= 2^31 planes or V * Nz * Nr * Nc >= 2^40 elements (plane counts are ints; element
+ * offsets are 64-bit).  Buffers need only be aligned to their element type.
+ * ------------------------------------------------------------------------------------------- */
+long long pdwt_ext3db_tmp_elems(int V, int Nz, int Nr, int Nc, int hlen, int levels);
+long long pdwt_ext3db_adjoint_tmp_elems(int V, int Nz, int Nr, int Nc, int hlen, int levels);
+int pdwt_ext3db_forward_f32(const float* d_src, float* const* d_bands, int V, int Nz, int Nr, int Nc, int levels, int mode, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext3db_forward_f64(const double* d_src, double* const* d_bands, int V, int Nz, int Nr, int Nc, int levels, int mode, const pdwt_filters_f64* f, double* d_tmp);
+int pdwt_ext3db_inverse_f32(float* d_dst, float* const* d_bands, int V, int Nz, int Nr, int Nc, int levels, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext3db_inverse_f64(double* d_dst, double* const* d_bands, int V, int Nz, int Nr, int Nc, int levels, const pdwt_filters_f64* f, double* d_tmp);
+int pdwt_ext3db_forward_adjoint_f32(float* d_dst, float* const* d_bands, int V, int Nz, int Nr, int Nc, int levels, int mode, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext3db_forward_adjoint_f64(double* d_dst, double* const* d_bands, int V, int Nz, int Nr, int Nc, int levels, int mode, const pdwt_filters_f64* f, double* d_tmp);
+int pdwt_ext3db_inverse_adjoint_f32(const float* d_src, float* const* d_bands, int V, int Nz, int Nr, int Nc, int levels, const pdwt_filters_f32* f, float* d_tmp);
+int pdwt_ext3db_inverse_adjoint_f64(const double* d_src, double* const* d_bands, int V, int Nz, int Nr, int Nc, int levels, const pdwt_filters_f64* f, double* d_tmp);
+
+/* ---------------------------------------------------------------------------------------------
  * Batched 1-D wavelet packets (pdwt_amd/csrc/wpt1d.hip; the class: WaveletPackets1D, include/wpt1d.h): the full binary tree of
  * every row of an Nr x Nc batch -- pywt.WaveletPacket(mode='periodization'), natural (Paley) order.  Depth l has 2^l nodes per row
  * of n_l = div2(n_{l-1}) samples (n_0 = Nc); node i has the children 2i (a) and 2i + 1 (d) of depth l + 1: the [A, D] bands of one

@@ -91,7 +91,7 @@ PLAIN_SYMBOLS = ["pdwt_device_count", "pdwt_set_device", "pdwt_get_device", "pdw
                  "pdwt_num_bands_ext1d", "pdwt_ext1d_band_len", "pdwt_ext1d_fused", "pdwt_ext1d_tmp_elems",
                  "pdwt_ext2db_fused", "pdwt_ext2db_tmp_elems", "pdwt_ext2db_adjoint_tmp_elems", "pdwt_ext1d_adjoint_tmp_elems",
                  "pdwt_num_bands_ext3d", "pdwt_ext3d_band_shape", "pdwt_ext3d_tmp_elems", "pdwt_ext3d_tmp_approx_offset",
-                 "pdwt_ext3d_adjoint_level_tmp_elems", "pdwt_ext3d_adjoint_z_run",
+                 "pdwt_ext3d_adjoint_level_tmp_elems", "pdwt_ext3d_adjoint_z_run", "pdwt_ext3db_tmp_elems", "pdwt_ext3db_adjoint_tmp_elems",
                  "pdwt_wp1_geometry", "pdwt_wp1_fused", "pdwt_wp1_tmp_elems", "pdwt_wp1_frequency_order", "pdwt_wp1_state_table", "pdwt_memcpy2d",
                  "pdwt_wptb_geometry", "pdwt_wptb_fused", "pdwt_wptb_lds_bytes", "pdwt_wptb_tmp_elems", "pdwt_wptb_state_table", "pdwt_wptb_chunk_lists"]
 TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coeffs_buffer", "copy_coeffs_buffer",
@@ -104,6 +104,7 @@ TYPED_SYMBOLS = (["compute_filters_separable", "create_coeffs_buffer", "free_coe
                   "wpt2d_forward_level", "wpt2d_inverse_level", "wpt2d_node_cost", "ext2d_forward_level", "ext2d_inverse_level",
                   "ext1d_forward_level", "ext1d_inverse_level", "ext1d_forward", "ext1d_inverse",
                   "ext3d_forward_level", "ext3d_inverse_level", "ext3d_forward_adjoint_level", "ext3d_inverse_adjoint_level",
+                  "ext3db_forward", "ext3db_inverse", "ext3db_forward_adjoint", "ext3db_inverse_adjoint",
                   "ext2db_forward_level", "ext2db_inverse_level", "ext2db_forward", "ext2db_inverse",
                   "ext2db_forward_adjoint_level", "ext2db_forward_adjoint", "ext2db_inverse_adjoint",
                   "ext1d_forward_adjoint_level", "ext1d_forward_adjoint", "ext1d_inverse_adjoint",
@@ -256,6 +257,10 @@ def hip():
         # their adjoints: (dst, HOST table of the 8 cotangent bands, nz, nr, nc, mode, bank, scratch) / (src, table, nz, nr, nc, bank, scratch)
         getattr(L, "pdwt_ext3d_forward_adjoint_level_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, C.POINTER(FT), vp]
         getattr(L, "pdwt_ext3d_inverse_adjoint_level_" + sfx).argtypes = [vp, C.POINTER(vp), ci, ci, ci, C.POINTER(FT), vp]
+        for name in ("forward", "forward_adjoint"):
+            getattr(L, "pdwt_ext3db_%s_%s" % (name, sfx)).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, ci, ci, C.POINTER(FT), vp]
+        for name in ("inverse", "inverse_adjoint"):
+            getattr(L, "pdwt_ext3db_%s_%s" % (name, sfx)).argtypes = [vp, C.POINTER(vp), ci, ci, ci, ci, ci, C.POINTER(FT), vp]
         # batched 2-D with boundary modes: one level of B images (src, A, H, V, D stacks, B, nr, nc, [mode,] bank); all levels (src or dst,
         # HOST table of 3 * levels + 1 device pointers, B, Nr, Nc, levels, [mode,] bank, scratch or NULL) -> 1 fused / 0 per level / < 0
         getattr(L, "pdwt_ext2db_forward_level_" + sfx).argtypes = [vp, vp, vp, vp, vp, ci, ci, ci, ci, C.POINTER(FT)]
@@ -306,6 +311,10 @@ def hip():
     L.pdwt_ext3d_adjoint_level_tmp_elems.restype = C.c_longlong
     L.pdwt_ext3d_adjoint_level_tmp_elems.argtypes = [ci, ci, ci, ci]
     L.pdwt_ext3d_adjoint_z_run.argtypes = [ci, ci, ci, C.POINTER(ci), C.POINTER(ci)]
+    L.pdwt_ext3db_tmp_elems.restype = C.c_longlong
+    L.pdwt_ext3db_tmp_elems.argtypes = [ci, ci, ci, ci, ci, ci]
+    L.pdwt_ext3db_adjoint_tmp_elems.restype = C.c_longlong
+    L.pdwt_ext3db_adjoint_tmp_elems.argtypes = [ci, ci, ci, ci, ci, ci]
     L.pdwt_num_bands_ext1d.argtypes = [ci, ci, ci]
     L.pdwt_ext1d_band_len.restype = C.c_longlong
     L.pdwt_ext1d_band_len.argtypes = [ci, ci, ci, ci]

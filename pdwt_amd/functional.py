@@ -1,5 +1,5 @@
 """Differentiable boundary-mode DWT for torch device tensors: a stateless layer over the C-ABI drivers of include/pdwt_hip.h
-("Batched 2-D / 1-D DWT with boundary modes", "3-D DWT with boundary modes" and the two "Adjoints ..." sections).
+("Batched 2-D / 1-D DWT with boundary modes", "Batched 3-D DWT with boundary modes" and the "Adjoints ..." sections).
 
     bands = dwt2(x, "db2", levels=2, mode="symmetric")   # x: (..., Nr, Nc) -> [A_L, H1, V1, D1, ..., H_L, V_L, D_L], each (..., nr_l, nc_l)
     x     = idwt2(bands, (Nr, Nc), "db2")
@@ -247,7 +247,7 @@ def _idwt1(bands, n, wname, mode=None):
     return out
 
 
-# ---- 3-D: the level entries, one volume per call (leading axes loop; the levels loop here) --------------------------------------------
+# ---- 3-D: a stack of volumes per driver call (the leading axes are the stack; the drivers loop the levels) -------------------------------
 def _shape3(shape):
     if len(shape) != 3 or any(int(v) != v or int(v) < 1 for v in shape):
         raise ValueError("shape must be (Nz, Nr, Nc), not %r" % (tuple(shape),))
@@ -255,48 +255,18 @@ def _shape3(shape):
 
 
 def _geom3(shape3, hlen, levels):
-    """([(nz_l, nr_l, nc_l) for l = 0 .. levels], scratch elements): every level is one the level entries take"""
+    """[(nz_l, nr_l, nc_l) for l = 0 .. levels]: every level is one the level entries and their adjoints take"""
     axes = [_axis_lengths(n, hlen, levels, what) for n, what in zip(shape3, ("z", "row", "column"))]
     shapes = [tuple(a[l] for a in axes) for l in range(levels + 1)]
     L = N.hip()
-    tmp = 0
     for l in range(levels):
-        e = L.pdwt_ext3d_adjoint_level_tmp_elems(shapes[l][0], shapes[l][1], shapes[l][2], hlen)
-        if e < 0:
+        if L.pdwt_ext3d_adjoint_level_tmp_elems(shapes[l][0], shapes[l][1], shapes[l][2], hlen) < 0:
             raise ValueError("level %d: a %d x %d x %d volume is a size the level drivers refuse" % ((l + 1,) + shapes[l]))
-        tmp = max(tmp, e)
-    return shapes, tmp
+    return shapes
 
 
 def _table_shapes3(shapes, levels):
     return [shapes[levels]] + [shapes[l] for l in range(levels, 0, -1) for _ in range(7)]
-
-
-class _Calls3:
-    """the calls of one operator: the device check once, then per call the producer / consumer ordering of _run"""
-
-    def __init__(self, sfx, like, tmp_elems):
-        torch = _torch()
-        self.L = N.hip()
-        if like.device.index is not None and like.device.index != self.L.pdwt_get_device():
-            raise ValueError("the tensors live on device %d, the library runs on device %d (pdwt_set_device)" % (like.device.index, self.L.pdwt_get_device()))
-        self.sfx, self.es = sfx, like.element_size()
-        self.tmp = torch.empty(int(tmp_elems), dtype=like.dtype, device=like.device)
-
-    def scratch(self, like, shapes):
-        return [like.new_empty(s) for s in shapes]
-
-    def ptr(self, t, volume, shape):
-        return t.data_ptr() + volume * shape[0] * shape[1] * shape[2] * self.es
-
-    def __call__(self, name, *args):
-        L = self.L
-        _sync_producer()
-        rc = getattr(L, "pdwt_%s_%s" % (name, self.sfx))(*args, C.c_void_p(self.tmp.data_ptr()))
-        if rc < 0:
-            raise RuntimeError("pdwt_%s_%s failed (%d): %s" % (name, self.sfx, rc, (L.pdwt_last_error_string() or b"").decode()))
-        if L.pdwt_sync() != 0:
-            raise RuntimeError("pdwt_sync failed: %s" % (L.pdwt_last_error_string() or b"").decode())
 
 
 def _dwt3(x, wname, levels, mode, adjoint_of_inverse=False):
@@ -305,53 +275,42 @@ def _dwt3(x, wname, levels, mode, adjoint_of_inverse=False):
         raise ValueError("a tensor of shape (..., Nz, Nr, Nc) is required")
     levels, f = _levels(levels, MAX_LEVELS_3D), _bank(wname, sfx)
     m = 0 if adjoint_of_inverse else _mode(mode)
-    lead, shape = tuple(x.shape[:-3]), _shape3(x.shape[-3:])
-    shapes, tmp = _geom3(shape, f.hlen, levels)
+    lead, (Nz, Nr, Nc) = tuple(x.shape[:-3]), _shape3(x.shape[-3:])
+    shapes = _geom3((Nz, Nr, Nc), f.hlen, levels)
     V = _count(lead, (1 << 31) - 1, "volumes")
-    tshapes = _table_shapes3(shapes, levels)
-    bands = [x.new_empty(lead + s) for s in tshapes]
-    run = _Calls3(sfx, x, tmp)
-    approx = run.scratch(x, shapes[1:levels])  # aaa of the levels 1 .. levels - 1 of one volume: never x, never a band
-    for v in range(V):
-        for l in range(1, levels + 1):
-            src = run.ptr(x, v, shape) if l == 1 else approx[l - 2].data_ptr()
-            aaa = run.ptr(bands[0], v, shapes[levels]) if l == levels else approx[l - 1].data_ptr()
-            k0 = 1 + 7 * (levels - l)
-            tab = (C.c_void_p * 8)(aaa, *[run.ptr(b, v, shapes[l]) for b in bands[k0:k0 + 7]])
-            nz, nr, nc = shapes[l - 1]
-            if adjoint_of_inverse:
-                run("ext3d_inverse_adjoint_level", C.c_void_p(src), tab, nz, nr, nc, C.byref(f))
-            else:
-                run("ext3d_forward_level", C.c_void_p(src), tab, nz, nr, nc, m, C.byref(f))
+    L = N.hip()
+    bands = [x.new_empty(lead + s) for s in _table_shapes3(shapes, levels)]
+    tab = _table(bands)
+    if adjoint_of_inverse:
+        _run("ext3db_inverse_adjoint", sfx, x, L.pdwt_ext3db_tmp_elems(V, Nz, Nr, Nc, f.hlen, levels),  # (the forward in mode zero: no frames)
+             lambda fn, t: fn(C.c_void_p(x.data_ptr()), tab, V, Nz, Nr, Nc, levels, C.byref(f), t))
+    else:
+        _run("ext3db_forward", sfx, x, L.pdwt_ext3db_tmp_elems(V, Nz, Nr, Nc, f.hlen, levels),
+             lambda fn, t: fn(C.c_void_p(x.data_ptr()), tab, V, Nz, Nr, Nc, levels, m, C.byref(f), t))
     return bands
 
 
 def _idwt3(bands, shape, wname, mode=None):
-    """mode None: the inverse; a mode: the adjoint of the forward transform.  Coarse to fine: the output of a level is aaa of the next"""
+    """mode None: the inverse; a mode: the adjoint of the forward transform"""
     bands, sfx, levels = _band_list(bands, 7, MAX_LEVELS_3D)
     f = _bank(wname, sfx)
     m = None if mode is None else _mode(mode)
-    shape = _shape3(shape)
-    shapes, tmp = _geom3(shape, f.hlen, levels)
+    Nz, Nr, Nc = _shape3(shape)
+    shapes = _geom3((Nz, Nr, Nc), f.hlen, levels)
     if bands[0].dim() < 3:
         raise ValueError("bands of shape (..., nz, nr, nc) are required")
     lead = tuple(bands[0].shape[:-3])
     _check_shapes(bands, lead, _table_shapes3(shapes, levels))
     V = _count(lead, (1 << 31) - 1, "volumes")
-    out = bands[0].new_empty(lead + shape)
-    run = _Calls3(sfx, out, tmp)
-    approx = run.scratch(out, shapes[1:levels])
-    for v in range(V):
-        for l in range(levels, 0, -1):
-            aaa = run.ptr(bands[0], v, shapes[levels]) if l == levels else approx[l - 1].data_ptr()
-            dst = run.ptr(out, v, shape) if l == 1 else approx[l - 2].data_ptr()
-            k0 = 1 + 7 * (levels - l)
-            tab = (C.c_void_p * 8)(aaa, *[run.ptr(b, v, shapes[l]) for b in bands[k0:k0 + 7]])
-            nz, nr, nc = shapes[l - 1]
-            if m is None:
-                run("ext3d_inverse_level", C.c_void_p(dst), tab, nz, nr, nc, C.byref(f))
-            else:
-                run("ext3d_forward_adjoint_level", C.c_void_p(dst), tab, nz, nr, nc, m, C.byref(f))
+    L = N.hip()
+    out = bands[0].new_empty(lead + (Nz, Nr, Nc))
+    tab = _table(bands)
+    if m is None:
+        _run("ext3db_inverse", sfx, out, L.pdwt_ext3db_tmp_elems(V, Nz, Nr, Nc, f.hlen, levels),
+             lambda fn, t: fn(C.c_void_p(out.data_ptr()), tab, V, Nz, Nr, Nc, levels, C.byref(f), t))
+    else:
+        _run("ext3db_forward_adjoint", sfx, out, L.pdwt_ext3db_adjoint_tmp_elems(V, Nz, Nr, Nc, f.hlen, levels),
+             lambda fn, t: fn(C.c_void_p(out.data_ptr()), tab, V, Nz, Nr, Nc, levels, m, C.byref(f), t))
     return out
 
 
