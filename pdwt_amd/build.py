@@ -23,7 +23,7 @@ INC = os.path.join(ROOT, "include")
 HIP_SOURCES = ["dwt_lat.hip", "dwt_ext2db.hip", "wpt2db.hip", "swt_fused_l2_fwd.hip", "swt_fused_l2_inv.hip", "swt_fused_l2_inv1.hip", "swt_fused_l2_inv2.hip", "swt_fused_l2_inv4.hip", "dwt_lds.hip", "dwt_casc_inv3.hip", "dwt_casc.hip", "dwt_casc_invw.hip", "swt_fused_inv.hip", "swt_fused_invp.hip", "swt_fused_fwd.hip", "swt_fused_fwd_long.hip", "swt_fused_inv_long.hip", "swt_fused_f64_fwd.hip", "swt_fused_f64_inv.hip", "dwt1d_fused.hip", "dwt1d_fused_nt.hip", "dwt_stream.hip", "cols_ring_dwt_f32.hip", "cols_ring_dwt_f64.hip", "cols_ring_swt_f32.hip", "cols_ring_swt_f64.hip", "rows_tr.hip", "runtime.hip", "coeffs.hip", "dwt.hip", "swt.hip", "haar.hip", "utils.hip", "bandstats.hip", "bandbatch.hip", "nonsep.hip", "dwt3d.hip", "swt3d.hip", "wpt2d.hip", "dwt_ext.hip", "dwt_ext1d.hip", "dwt_ext_adj.hip", "dwt_ext3d_adj.hip", "dwt_ext3db.hip", "wpt1d.hip", "dwt_ext3d.hip", "collective.hip", "selfcheck.hip", "filters.cpp"]
 HOST_SOURCES = ["wt.cpp", "wt_capi.cpp", "wt3d.cpp", "wpt.cpp", "wt_ext.cpp"]
 # (kept for reference; an object's real dependencies are the files its source includes, transitively: _deps())
-HIP_DEPS = ["common.hpp", "dwt_stream.hpp", "stream_dev.hpp", "dwt_casc.hpp", "casc_dev.hpp", "dwt_lds.hpp", "swt_fused.hpp", "swt_fused.inc", "swt_fused_l2.inc", "swt_fused_f64.inc", "dwt1d_fused.hpp", "cols_ring.hpp", "cols_ring.inc", "rows_tr.hpp", "tapreg.hpp", "filters_table.inc", "bandlist.hpp", "vol3d.hpp", "tile_stages.hpp", "image_stages.hpp", "dwt_ext.hpp", "dwt_ext1d.hpp", "wpt1d.hpp", "dwt_ext3d_xy.hpp", "dwt_ext2db.hpp", "wpt2db.hpp", "dwt_ext_adj.hpp", "dwt_ext3d_adj.hpp", "dwt_ext3db.hpp"]
+HIP_DEPS = ["common.hpp", "dwt_stream.hpp", "stream_dev.hpp", "dwt_casc.hpp", "casc_dev.hpp", "dwt_lds.hpp", "swt_fused.hpp", "swt_fused.inc", "swt_fused_l2.inc", "swt_fused_f64.inc", "dwt1d_fused.hpp", "cols_ring.hpp", "cols_ring.inc", "rows_tr.hpp", "tapreg.hpp", "filters_table.inc", "bandlist.hpp", "vol3d.hpp", "tile_stages.hpp", "image_stages.hpp", "dwt_ext.hpp", "dwt_ext1d.hpp", "wpt1d.hpp", "dwt_ext3d_xy.hpp", "dwt_ext2db.hpp", "wpt2db.hpp", "dwt_ext_adj.hpp", "z_stages.hpp", "dwt_ext3d_level.hpp"]
 ARCH = "gfx950"
 
 

@@ -6,12 +6,12 @@
 //             z:   4 quadrants      -> the 8 bands (hz, hy, hx)           lanes across a plane, 16 outputs per thread along z
 //   inverse   z first (bands -> quadrants), then x-y (quadrants -> volume).
 // The x-y kernels are the shared tile stages of tile_stages.hpp (with the packet and the boundary-mode tile kernels) on one plane; the
-// z kernels are written here.
+// z kernels are those of z_stages.hpp (with the boundary-mode volume transforms), instantiated here for the periodised window.
 // Per output sample the tap order and the one-FMA-per-tap accumulation are the oracle's: the 3-D result is bit-identical to
 // composing the 1-D level along the axes (Haar excepted, within 1 ulp: the oracle's 1-D Haar level scales a +- b in double).
 // Traffic per level: one read of the input (plus the tile halos) and one write of the quadrants, then one read of the quadrants
 // and one write of the bands -- twice the compulsory bytes of a fully fused level.
-#include "tile_stages.hpp"
+#include "z_stages.hpp"
 
 namespace pdwt {
 
@@ -62,104 +62,21 @@ __global__ __launch_bounds__(kTileThreads) void k_inv_xy(XYJob<T> job, Taps2<T> 
     tile_rows_synthesis_write<T, HL, SH, WC, TIY, TIX, kTileThreads>(cb, taps, job.dst + (size_t)z * job.ny * job.nx, job.ny, job.nx, g0y, g0x, tid);
 }
 
-// ---- z pass: ZC outputs per thread along z from a register window -----------------------------------------
-// Lanes run across a plane (coalesced), blockIdx.y = chunk of ZC outputs along z, blockIdx.z = quadrant.  The thread loads the
-// 2*ZC + HL - 2 input planes of its chunk ONCE into registers and computes every output of the chunk from them.  These loops read the
-// taps straight from the kernel argument and are therefore written here, not in tile_stages.hpp: a function that takes the taps
-// by reference makes the compiler load all 2 * HL of them at the kernel's entry, which does not fit the SGPRs of a long float64 bank.
-constexpr int kZThreads = 256;
-constexpr int ZC = 16;
-
-template <typename T>
-struct ZJob {
-    const T* src[4];  // forward: quadrants (nz planes); inverse: low branches (nin planes)
-    const T* src2[4]; // inverse: high branches
-    T* lo[4];         // forward: low outputs; inverse: outputs
-    T* hi[4];         // forward: high outputs
-    int nin, nout, plane;
-};
-
+// ---- z pass: k_z_analysis / k_z_synthesis of z_stages.hpp, periodised, on the quadrants of one volume (ZJob) -----------------------
 template <typename T, int HL>
-__global__ __launch_bounds__(kZThreads) void k_ana_z(ZJob<T> job, Taps2<T> taps)
+static int launch_xy(bool fwd, const XYJob<T>& xy, int nz, const Taps2<T>& taps)
 {
-    const int k = blockIdx.x * kZThreads + threadIdx.x;
-    if (k >= job.plane) return;
-    const int e = blockIdx.z, i0 = blockIdx.y * ZC;
-    constexpr int c = HL / 2 - 1, W = 2 * ZC + HL - 2;
-    const int n = job.nin, s0 = 2 * i0 - c;
-    const size_t pl = (size_t)job.plane;
-    const T* __restrict__ x = job.src[e] + k;
-    T v[W];
-#pragma unroll
-    for (int w = 0; w < W; w++) v[w] = x[(size_t)wrap_ext(s0 + w, n) * pl];
-    T* __restrict__ lo = job.lo[e] + k;
-    T* __restrict__ hi = job.hi[e] + k;
-#pragma unroll
-    for (int u = 0; u < ZC; u++) {
-        if (i0 + u < job.nout) {
-            T sl = T(0), sh = T(0);
-#pragma unroll
-            for (int j = 0; j < HL; j++) {
-                sl = fma_t<T>(v[2 * u + j], taps.a[HL - 1 - j], sl);
-                sh = fma_t<T>(v[2 * u + j], taps.b[HL - 1 - j], sh);
-            }
-            lo[(size_t)(i0 + u) * pl] = sl;
-            hi[(size_t)(i0 + u) * pl] = sh;
-        }
-    }
+    const size_t lds = fwd ? tile_fwd_lds<T, HL>(false) : tile_inv_lds<T, HL>(true);
+    const dim3 grid = fwd ? dim3(idiv_up(xy.hx, TFX), idiv_up(xy.hy, TFY), nz) : dim3(idiv_up(xy.nx, TIX), idiv_up(xy.ny, TIY), nz);
+    return launch_lds(fwd ? k_fwd_xy<T, HL> : k_inv_xy<T, HL>, grid, dim3(kTileThreads), lds, xy, taps);
 }
 
-template <typename T, int HL>
-__global__ __launch_bounds__(kZThreads) void k_syn_z(ZJob<T> job, Taps2<T> taps)
-{
-    const int k = blockIdx.x * kZThreads + threadIdx.x;
-    if (k >= job.plane) return;
-    const int e = blockIdx.z, g0 = blockIdx.y * ZC;  // even
-    constexpr int h2 = HL / 2, c = h2 / 2, shift = syn_shift(HL), W = ZC / 2 + h2;
-    const int nin = job.nin, q0 = g0 / 2 - c;
-    const size_t pl = (size_t)job.plane;
-    const T* __restrict__ a = job.src[e] + k;
-    const T* __restrict__ d = job.src2[e] + k;
-    T va[W], vd[W];
-#pragma unroll
-    for (int w = 0; w < W; w++) {
-        const size_t s = (size_t)wrap_per(q0 + w, nin) * pl;
-        va[w] = a[s];
-        vd[w] = d[s];
-    }
-    T* __restrict__ out = job.lo[e] + k;
-#pragma unroll
-    for (int u = 0; u < ZC; u++) {
-        if (g0 + u < job.nout) {
-            const int gp = u + shift, lp = gp >> 1, off = 1 - (gp & 1);  // compile-time after unrolling
-            T sa = T(0), sd = T(0);
-#pragma unroll
-            for (int j = 0; j < h2; j++) {
-                sa = fma_t<T>(va[lp + j], taps.a[HL - 1 - (2 * j + off)], sa);
-                sd = fma_t<T>(vd[lp + j], taps.b[HL - 1 - (2 * j + off)], sd);
-            }
-            out[(size_t)(g0 + u) * pl] = sa + sd;
-        }
-    }
-}
-
-template <typename T, int HL>
-static int launch_level(int dir, int pass, const XYJob<T>& xy, const ZJob<T>& zj, int nz, const Taps2<T>& taps)
-{
-    if (pass == 0) {  // x-y
-        const bool fwd = dir == 0;
-        const size_t lds = fwd ? tile_fwd_lds<T, HL>(false) : tile_inv_lds<T, HL>(true);
-        const dim3 grid = fwd ? dim3(idiv_up(xy.hx, TFX), idiv_up(xy.hy, TFY), nz) : dim3(idiv_up(xy.nx, TIX), idiv_up(xy.ny, TIY), nz);
-        return launch_lds(fwd ? k_fwd_xy<T, HL> : k_inv_xy<T, HL>, grid, dim3(kTileThreads), lds, xy, taps);
-    }
-    const dim3 grid(idiv_up(zj.plane, kZThreads), idiv_up(zj.nout, ZC), 4);  // z
-    return launch_lds(dir == 0 ? k_ana_z<T, HL> : k_syn_z<T, HL>, grid, dim3(kZThreads), 0, zj, taps);
-}
-
+// pass 0: x-y; pass 1: z over the four quadrants
 template <typename T>
 static int run_pass(int hlen, int dir, int pass, const XYJob<T>& xy, const ZJob<T>& zj, int nz, const Taps2<T>& taps)
 {
-    return with_filter_length(hlen, [&](auto hl) { return launch_level<T, decltype(hl)::value>(dir, pass, xy, zj, nz, taps); });
+    if (pass == 1) return run_z<true, T>(hlen, dir == 0, zj, 4, taps);
+    return with_filter_length(hlen, [&](auto hl) { return launch_xy<T, decltype(hl)::value>(dir == 0, xy, nz, taps); });
 }
 
 // ---- geometry ------------------------------------------------------------------------------------

@@ -9,11 +9,12 @@
 // of its window with the taps HL-2-2m (gp even) / HL-1-2m (gp odd), where gp = g + SHIFT.  Boundary modes: SHIFT = 0, the window starts at
 // coefficient g0 / 2.  Periodised: SHIFT = syn_shift(HL), the window starts HL/4 coefficients earlier (and is one coefficient longer).
 //
-// Not folded onto this header, on purpose: the z register-window kernels of dwt3d.hip and dwt_ext3d.hip (their loops unroll completely
-// and read the taps straight from the kernel argument; behind a function that takes the taps by reference the compiler loads all
-// 2 * HL taps at the kernel's entry, and the float64 banks of 22 taps and more spill SGPRs); swt3d.hip (sublattice addressing, chunked
+// Not folded onto this header, on purpose: the z register-window kernels of the volume transforms and the z adjoint (their loops unroll
+// completely and read the taps straight from the kernel argument; behind a function that takes the taps by reference the compiler loads
+// all 2 * HL taps at the kernel's entry, and the float64 banks of 22 taps and more spill SGPRs -- they are written once as kernel
+// templates on the job in z_stages.hpp, which keeps the taps in the kernel's own body); swt3d.hip (sublattice addressing, chunked
 // tap reloads in fma_taps2, an inverse that stages one x band at a time); the whole-image-in-LDS kernels with run-time geometry
-// (their 2-D stages are shared in image_stages.hpp, the 1-D ones in dwt_ext1d.hpp / wpt1d.hpp); k_ext3_adj_z (dwt_ext3d_adj.hpp); the Haar and cost kernels of wpt2d.hip.
+// (their 2-D stages are shared in image_stages.hpp, the 1-D ones in dwt_ext1d.hpp / wpt1d.hpp); the Haar and cost kernels of wpt2d.hip.
 #pragma once
 #include "vol3d.hpp"
 
